@@ -3,6 +3,7 @@
 
     python bench.py                                  # 1 GPU, workload S2 (100k poses / 10k landmarks / 720 beams)
     python bench.py --gpus N --steps K --warmup W    # starts the N ranks itself (fresh child processes)
+    python bench.py ... --dump-outputs DIR           # also writes the timed path's last result as DIR/*.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W      # or is started as one of them
 
@@ -45,6 +46,7 @@ HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6300 ach
 FP64_VALU_PEAK_TFLOPS = 78.6  # 256 CUs x 4 SIMDs x 16 FP64 FMA lanes x 2 x 2.4 GHz (no MFMA on this path)
 MAX_SWEEPS_WITHOUT_REWIND = 40   # S2 leaves the association gate after ~50 consecutive sweeps
 RESET_EVERY = 12
+DUMP_MAX_BYTES = 64 << 20        # --dump-outputs: all arrays together
 
 
 def algorithmic_bytes(kernel, nnz, E, nloc, L, nlaunch, hier=True, runs=0):
@@ -482,6 +484,25 @@ def _assoc_record(eng):
             "runs": runs, "runs_taken_beam_by_beam_so_far": bbb}
 
 
+def dump_outputs(job, out_dir):
+    """--dump-outputs: what the timed path computed in its last step, as its caller receives it (get_state: poses x (3,T),
+    map (2,L) zero padded, landmark counts (L), landmark count K), one float64 DIR/<name>.npy each, so that two builds can
+    be compared output for output on the same seeded workload.  Collective in a sharded job (every rank calls it); rank 0
+    writes.  Above DUMP_MAX_BYTES the poses are a fixed, seeded sample of columns (x_columns.npy holds their indices)."""
+    x, mapa, counts, K = (job.runner if job.sharded else job.eng).get_state()
+    if job.rank != 0:
+        return
+    out = {"x": x, "map": mapa, "counts": counts, "K": np.array([K])}
+    budget = DUMP_MAX_BYTES - 1024                      # (1 KB for the .npy headers)
+    if sum(a.nbytes for a in out.values()) > budget:
+        keep = (budget - mapa.nbytes - counts.nbytes - 8) // (4 * 8)   # a kept pose: 3 values + its index
+        cols = np.sort(np.random.default_rng(0).choice(x.shape[1], keep, replace=False))
+        out.update(x=x[:, cols], x_columns=cols)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def dropin_record(job, steps, warmup):
     """The reference's own call: mapa_refinado, x = ICM.iterations_process_offline(mapa_viejo, x)
     (scripts/ICM_ROS.py:298-311 driver loop), host NumPy arrays in and out every sweep -- PCIe
@@ -683,8 +704,10 @@ def run_rank(args):
         total = args.steps + args.warmup
         if total > MAX_SWEEPS_WITHOUT_REWIND and not args.no_rewind and factory is None:
             job.enable_rewind()
-        # three timed windows of K sweeps over the same states; the record is the MEDIAN window, the others are listed
+        # --windows timed windows of K sweeps over the same states; the record is the MEDIAN window, the others are listed
         wins = sorted(job.timed(args.steps, args.warmup, windows=args.windows))
+        if mode == args.scaling and args.dump_outputs:
+            dump_outputs(job, args.dump_outputs)
         elapsed = wins[len(wins) // 2]
         ms = 1e3 * elapsed / max(args.steps, 1)
         rec = {"value": round((T - 1) * args.steps / elapsed, 1), "ms_per_step": round(ms, 4),
@@ -720,7 +743,7 @@ def run_rank(args):
                    "association": _assoc_record(job.eng) if world == 1 else "geometric runs (bounding-circle test, beam by beam where it does not settle)",
                    "fixup_poses": job.eng.fixup_poses() if hasattr(job.eng, "fixup_poses") else None,
                    "state_rewind": ("initial state restored on the device every %d sweeps" % RESET_EVERY) if job.rewind
-                   else "none inside a timed window: %d consecutive sweeps from the initial state per window" % (args.steps + args.warmup + 1),
+                   else "none inside a timed window: %d consecutive sweeps from the initial state per window" % (args.steps + args.warmup + (args.windows > 1)),
                    "collectives_per_sweep": 0 if not sharded else "1 all-gather of [3L+16] f64 per rank (landmark statistics + the shard's boundary poses); no halo exchange (ghost pose)",
                    "collectives_issued_by": None if not sharded else
                    ("C library (ncclAllGather on the handle's stream)" if args.collectives == "library" and factory is None
@@ -734,7 +757,8 @@ def run_rank(args):
     if factory is None and not args.no_roofline:
         out["roofline"] = roofline(job, main_ms)
     if rank == 0 and world == 1 and factory is None and not args.no_extras:
-        out["dropin"] = dropin_record(job, max(args.steps // 2, 5), 2)
+        # consecutive sweeps without a rewind: kept below MAX_SWEEPS_WITHOUT_REWIND whatever --steps is
+        out["dropin"] = dropin_record(job, min(max(args.steps // 2, 5), MAX_SWEEPS_WITHOUT_REWIND - 2), 2)
     wl, cfg = job.wl, job.cfg
     if rank == 0 and world == 1 and factory is None and args.cpu_poses != 0:
         n_c = args.cpu_poses if args.cpu_poses > 0 else {"S2": 2500, "S1": 10000}.get(args.workload, job.T)
@@ -786,7 +810,8 @@ def main():
     ap.add_argument("--cpu-poses", type=int, default=-1, help="prefix length of the CPU baseline (0 = skip)")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the drop-in and config-3 records")
-    ap.add_argument("--windows", type=int, default=3, help="timed windows of --steps sweeps each over the same states (median reported)")
+    ap.add_argument("--windows", type=int, default=1,
+                    help="timed windows of --steps sweeps each over the same states (median reported); the default times exactly --steps sweeps")
     ap.add_argument("--no-rewind", action="store_true", help="never rewind the state, however many sweeps")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="strong",
                     help="N > 1: strong = the workload's sequence split N ways (BASELINE configs[4], the headline); "
@@ -798,7 +823,11 @@ def main():
                     help="drive even a 1-rank run through the sharded path (torch.distributed + RCCL all-gathers)")
     ap.add_argument("--device", choices=("cuda", "cpu"), default="cuda", help="cpu: launcher tests only (with --engine-factory)")
     ap.add_argument("--engine-factory", default="", help="test hook: module:function returning an engine double")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the state the last one computed as DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0 or args.windows < 1:
+        raise SystemExit("bench.py: --steps and --windows must be >= 1, --warmup >= 0")
     if args.device == "cpu" and not args.engine_factory:
         raise SystemExit("bench.py: there is no CPU path; --device cpu is for the launcher test with an engine double")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
