@@ -32,6 +32,7 @@
 #define ICM_BUILD_ID "unknown"
 #endif
 #include "icm_kernels.hip"
+static_assert(ICM_MAX_BEAMS == icm::kMaxBeams, "icmslam.h states the beam limit k_prefilter's LDS staging sets");
 
 using namespace icm;
 
@@ -122,7 +123,7 @@ struct icm_handle {
     DevBuf<double> mapx, mapy;
 
     // per-sweep
-    DevBuf<unsigned short> st_k;    // beams of every staged entry (<= B <= 8192: two bytes)
+    DevBuf<unsigned short> st_k;    // beams of every staged entry (<= B <= ICM_MAX_BEAMS: two bytes)
     DevBuf<int> label, bloc, st_label, nent, isnew, ent_off, new_rank, e_val, e_k, sval, lm_off, flags, scan_tot;
     DevBuf<unsigned> e_key, skey;
     DevBuf<double> st_sx, st_sy, pose_c, pose_m, btx, bty;
@@ -166,6 +167,7 @@ struct icm_handle {
     DevBuf<unsigned short> gh_st_k;
     hipEvent_t ev_gh0 = nullptr, ev_gh1 = nullptr;
     bool ghost_pending = false;   // the ghost chain of this sweep is queued on the solve stream (ev_gh1)
+    bool ghost_grid_wait = false; // ... and Mapa.filtrar, which rebuilds the search grid that chain reads, must wait for it
     int fused_spin_limit = 1 << 17;   // polls (x ~0.2 us) an even wave waits for its odd neighbours before deferring
     int fuse_colours = 1;    // 1: both colours of an unsharded red-black sweep in one launch (k_solve_m_fused)
     bool ms_clean = false;   // the [superchunk x L] matrix is zero (cleared by the last fused solve launch, launch_fused_solve)
@@ -570,7 +572,10 @@ int icm_upload(icm_handle* h, const double* ranges, const double* odo, const dou
     if (!h) return ICM_ERR_ARG;
     if (!ranges || !odo || !u || !cosb || !sinb) FAIL(h, ICM_ERR_ARG, "icm_upload: null pointer");
     if (T < 2 || B < 1 || t_begin < 0 || t_end > T || t_begin >= t_end) FAIL(h, ICM_ERR_ARG, "icm_upload: bad T/B/shard");
-    if (T > (1 << 30) || B > 8192 || (t_end - t_begin) * B > (int64_t)2000000000) FAIL(h, ICM_ERR_UNSUPPORTED, "icm_upload: sequence too large for 32-bit beam indices");
+    if (B > ICM_MAX_BEAMS)
+        FAIL(h, ICM_ERR_UNSUPPORTED, "icm_upload: B = " + std::to_string(B) + " beams per scan; the scan pre-filter stages at most ICM_MAX_BEAMS = " +
+                                         std::to_string(ICM_MAX_BEAMS) + " (4 waves x B x 28 bytes of LDS per workgroup)");
+    if (T > (1 << 30) || (t_end - t_begin) * B > (int64_t)2000000000) FAIL(h, ICM_ERR_UNSUPPORTED, "icm_upload: sequence too large for 32-bit beam indices");
     HIPCHK(h, hipSetDevice(h->device));
     h->T = T; h->B = B; h->t_begin = t_begin; h->nloc = t_end - t_begin;
     const size_t nr = (size_t)h->nloc * (size_t)B;
@@ -664,8 +669,8 @@ int icm_prefilter(icm_handle* h, int64_t* nnz_out) {
     const int nloc = (int)h->nloc, B = (int)h->B;
     HIPCHK(h, h->nkept.reserve((size_t)nloc + 1));
     HIPCHK(h, h->boff.reserve((size_t)nloc + 1));
-    const size_t lds = (size_t)kWavesPerBlock * (size_t)B * (3 * sizeof(double) + sizeof(int));
-    if (lds > 160 * 1024) FAIL(h, ICM_ERR_UNSUPPORTED, "icm_prefilter: too many beams per scan for the LDS staging");
+    const size_t lds = (size_t)B * kPrefilterLdsPerBeam;   // (B <= kMaxBeams: icm_upload)
+    if (lds > kLdsPerWorkgroup) FAIL(h, ICM_ERR_UNSUPPORTED, "icm_prefilter: too many beams per scan for the LDS staging");
     HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_prefilter<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_prefilter<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const int nb = nblocks_waves(nloc);
@@ -1289,6 +1294,7 @@ static int launch_ghost(icm_handle* h) {
     if (!h->timing) {   // (icm_sweep_solve makes the main stream wait for it in front of the solve launch)
         HIPCHK(h, hipEventRecord(h->ev_gh1, gs));
         h->ghost_pending = true;
+        h->ghost_grid_wait = true;
     }
     return ICM_OK;
 }
@@ -1425,6 +1431,14 @@ static int queue_filtrar(icm_handle* h, bool ev_map_recorded) {
     if (!(h->map_ev_in_local && h->map_by_spinner)) {   // (else the side stream already waits for the raw map: k_wait_word)
         if (!ev_map_recorded) HIPCHK(h, hipEventRecord(h->ev_map, h->stream));
         HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->ev_map, 0));
+    }
+    // The ghost pose's association (launch_ghost, solve stream) reads the search grid -- gpar, g_cell, g_lm, g_nb -- that
+    // Mapa.filtrar rebuilds for the next sweep: the side stream starts on it only once that chain is done.  (Without this
+    // wait a ghost scan slower than k_rec_push -- e.g. 180 runs, three batches with beam-by-beam fallbacks -- read a grid
+    // being rewritten, and the shard's first pose, solved against the ghost, came out wrong.)
+    if (h->ghost_grid_wait) {
+        HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->ev_gh1, 0));
+        h->ghost_grid_wait = false;
     }
     const size_t Ls = (size_t)L;
     if (h->world > 1)

@@ -40,6 +40,11 @@ namespace icm {
 
 constexpr int kBlock = 256;
 constexpr int kWavesPerBlock = kBlock / kWave;
+// Beams per scan k_prefilter can stage: each of its waves keeps B in-range beams (x, y, range, index: 28 bytes) in LDS,
+// and one workgroup may take a CU's whole 160 KiB.  icm_upload refuses a larger B (ICM_MAX_BEAMS of icmslam.h).
+constexpr size_t kPrefilterLdsPerBeam = (size_t)kWavesPerBlock * (3 * sizeof(double) + sizeof(int));
+constexpr size_t kLdsPerWorkgroup = 160 * 1024;
+constexpr int kMaxBeams = (int)(kLdsPerWorkgroup / kPrefilterLdsPerBeam);
 constexpr int kEmpty = (int)0x80000000;
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & (kWave - 1); }
@@ -1022,7 +1027,7 @@ void k_assoc_group(const double* __restrict__ x, const int* __restrict__ boff, c
         if (occ) {
             const unsigned q = (unsigned)(written + prefix_count(mask, lane));   // (scalar bases + 32-bit offsets, like the beam loads)
             *reinterpret_cast<int*>(reinterpret_cast<char*>(st_label + sbase) + (q << 2)) = k;
-            *reinterpret_cast<unsigned short*>(reinterpret_cast<char*>(st_k + sbase) + (q << 1)) = (unsigned short)T.cnt[s];   // (beams of one scan: <= B <= 8192)
+            *reinterpret_cast<unsigned short*>(reinterpret_cast<char*>(st_k + sbase) + (q << 1)) = (unsigned short)T.cnt[s];   // (beams of one scan: <= B <= kMaxBeams)
             *reinterpret_cast<double*>(reinterpret_cast<char*>(st_sbx + sbase) + (q << 3)) = T.sx[s];
             *reinterpret_cast<double*>(reinterpret_cast<char*>(st_sby + sbase) + (q << 3)) = T.sy[s];
             isnew |= k == -1;
@@ -1072,6 +1077,10 @@ void k_assoc_group(const double* __restrict__ x, const int* __restrict__ boff, c
 // ---------------------------------------------------------------------------------------
 constexpr int kRunCap = 64;        // beams per run at most (an unsettled run is one batch of the beam-by-beam path)
 constexpr int kRunUndecided = -3;
+static_assert(kRunCap <= kWave, "the beam-by-beam path of an unsettled run puts one beam per lane");
+// the run record packs k | first beam's offset in the pose << 16, and a staged entry's beam count is an unsigned short
+static_assert(kRunCap <= 0xffff && kMaxBeams - 1 <= 0xffff, "run record: k and the first beam's offset in 16 bits each");
+static_assert(kMaxBeams <= 0xffff, "st_k: beams of one entry (<= B) in an unsigned short");
 
 // One thread per pose cuts its kept beams into runs: a new run starts where the next body point is farther than `gap`
 // from the last one, farther than `ext` from the run's first point, or after kRunCap beams.  FILL = false counts the

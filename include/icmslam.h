@@ -36,6 +36,11 @@ extern "C" {
 #define ICM_RETRY_CAREFUL 1000   /* icm_sweep_finish only, after icm_set_optimistic(h, 1): a table overflowed on some
                                     rank, nothing was replaced; repeat the sweep's phase calls with icm_set_optimistic(h, 0) */
 
+/* Beams per scan (B of icm_upload) this build accepts: the scan pre-filter stages a whole scan per wave in LDS
+ * (4 waves x B x 28 bytes <= 160 KiB, one workgroup per CU).  icm_upload refuses a larger B with ICM_ERR_UNSUPPORTED
+ * before anything is launched. */
+#define ICM_MAX_BEAMS 1462
+
 #define ICM_SCHEDULE_SEQUENTIAL 0 /* reference Gauss-Seidel order (scripts/ICM_ROS.py:141) */
 #define ICM_SCHEDULE_REDBLACK 1   /* odd poses, then even poses (parallel)     */
 
@@ -71,7 +76,8 @@ int icm_set_stream(icm_handle *h, void *hip_stream);
  *   odo     [3*T], u [2*T]   full sequence, reference layout
  *   cosb,sinb [B]  cos/sin of the beam bearings (reference: k*pi/180,
  *           scripts/ICM_SLAM_tools.py:44,51), computed by the host
- * Single GPU: t_begin = 0, t_end = T. */
+ * Single GPU: t_begin = 0, t_end = T.  1 <= B <= ICM_MAX_BEAMS, else ICM_ERR_UNSUPPORTED (the handle keeps
+ * whatever it held before and accepts the next legal upload). */
 int icm_upload(icm_handle *h, const double *ranges, const double *odo, const double *u,
                const double *cosb, const double *sinb, int64_t T, int64_t B, int64_t t_begin,
                int64_t t_end);

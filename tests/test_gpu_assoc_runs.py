@@ -10,7 +10,7 @@ everywhere else in this suite and reported when they are not bit-identical.
 import numpy as np
 import pytest
 
-from util import Cfg, dataset, gold
+from util import Cfg, check_runs as _check_runs, dataset, gold
 
 pytestmark = pytest.mark.gpu
 
@@ -39,49 +39,6 @@ def _engine_synth(name):
     eng = SweepEngine(cfg)
     eng.upload(wl.scans, wl.odometry, wl.u, pose_major=True)
     return eng, wl.map_init.copy(), wl.x_init.copy(), wl.x0.copy()
-
-
-def _check_runs(eng, thr):
-    """Structure of the runs: a partition of every pose's kept beams into consecutive stretches, cut by the stated rule,
-    with a bounding circle that really bounds and the sum that really is the sum."""
-    off, bk, d, bx, by = eng.kept_beams()
-    roff, c, sb, r, k, f = eng.runs()
-    n_runs, _ = eng.run_counts()
-    assert roff[0] == 0 and roff[-1] == n_runs == len(k)
-    nb = np.diff(off)
-    pose_of_run = np.repeat(np.arange(len(nb)), np.diff(roff))
-    assert np.array_equal(np.bincount(pose_of_run, weights=k, minlength=len(nb)).astype(np.int64), nb), "the runs of a pose hold all its beams"
-    # consecutive: the first run starts at the pose's first beam, each next one where the last ended
-    first_of_pose = roff[:-1][np.diff(roff) > 0]
-    assert not f[first_of_pose].any()
-    same = pose_of_run[1:] == pose_of_run[:-1]
-    assert np.array_equal((f[:-1] + k[:-1])[same], f[1:][same])
-    assert k.min() >= 1 and k.max() <= 64
-    start = off[pose_of_run] + f                    # absolute index of each run's first beam
-    run_of_beam = np.repeat(np.arange(n_runs), k)   # (runs are in beam order)
-    assert np.array_equal(np.repeat(start, k) + (np.arange(len(run_of_beam)) - np.repeat(np.cumsum(k) - k, k)), np.arange(len(bx)))
-    # the sum and the circle
-    sx = np.bincount(run_of_beam, weights=bx, minlength=n_runs)
-    sy = np.bincount(run_of_beam, weights=by, minlength=n_runs)
-    assert np.abs(sb[:, 0] - sx).max() <= 1e-12 * max(1.0, np.abs(sx).max()) and np.abs(sb[:, 1] - sy).max() <= 1e-12 * max(1.0, np.abs(sy).max())
-    dist = np.hypot(bx - c[run_of_beam, 0], by - c[run_of_beam, 1])
-    assert (dist <= r[run_of_beam].astype(np.float64)).all(), "every beam inside its run's circle"
-    assert np.abs(c[:, 0] - sx / k).max() <= 1e-12 and np.abs(c[:, 1] - sy / k).max() <= 1e-12
-    # the cutting rule: inside a run, neighbours within the gap and everybody within the extent of the first beam
-    gap, ext = 0.35 * thr, 0.5 * thr
-    inner = np.ones(len(bx), dtype=bool)
-    inner[start] = False
-    j = np.flatnonzero(inner)
-    assert (np.hypot(bx[j] - bx[j - 1], by[j] - by[j - 1]) <= gap * (1 + 1e-12)).all()
-    assert (np.hypot(bx - bx[start][run_of_beam], by - by[start][run_of_beam]) <= ext * (1 + 1e-12)).all()
-    # ... and a run begins only where the rule asks for it
-    heads = start[f > 0]
-    prev_start = start[np.flatnonzero(f > 0) - 1]
-    g_ = np.hypot(bx[heads] - bx[heads - 1], by[heads] - by[heads - 1])
-    e_ = np.hypot(bx[heads] - bx[prev_start], by[heads] - by[prev_start])
-    full = k[np.flatnonzero(f > 0) - 1] == 64
-    assert ((g_ > gap * (1 - 1e-12)) | (e_ > ext * (1 - 1e-12)) | full).all()
-    return n_runs, float(k.mean()), float(r.max())
 
 
 @pytest.mark.parametrize("which", ["dataset", "tiny", "S1"])
