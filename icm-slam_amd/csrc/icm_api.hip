@@ -2674,6 +2674,17 @@ int icm_set_entry_path(icm_handle* h, int mode) {
 
 int icm_get_entry_path(const icm_handle* h) { return h ? h->path_used : ICM_ERR_ARG; }
 
+int icm_get_entry_layout(const icm_handle* h, int32_t* out5) {
+    if (!h || !out5) return ICM_ERR_ARG;
+    if (h->nchunks <= 0) return ICM_ERR_ARG;   // (laid out with the per-sweep buffers: after icm_upload)
+    out5[0] = h->chunk_poses;
+    out5[1] = h->chunk_group;
+    out5[2] = h->nsuper;
+    out5[3] = h->nchunks;
+    out5[4] = h->scan_ran ? 1 : 0;
+    return ICM_OK;
+}
+
 int icm_last_filtrar_info(const icm_handle* h, int64_t* out3) {
     if (!h || !out3) return ICM_ERR_ARG;
     out3[0] = h->lact;

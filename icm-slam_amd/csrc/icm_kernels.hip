@@ -1622,9 +1622,10 @@ __global__ __launch_bounds__(kBlock) void k_stats_prefix(const double* __restric
 //   k_rec_push   record prefix := (lower ranks) + matrix prefix + superchunk prefix.
 //   k_pose_moments_h then forms  target = (record prefix + entry prefix) / n  on the fly.
 // Everything streams or stays in LDS/L2: no global sort, no per-landmark gather/scatter.
-// A chunk with more than ~190 distinct landmarks, or a superchunk with more than kT2Cap,
-// raises flags[1]; the host then runs the sort-based pipeline (k_compact .. k_lm_scan), which
-// has no such limits.
+// A pose with more than kWave entries, a chunk with more than kT1 - 32 = 224 distinct labels or
+// a superchunk with more than kT2Cap = 1536 (fresh labels of landmark-creating poses counted
+// like the others) raises flags[1]; the host then runs the sort-based pipeline (k_compact ..
+// k_lm_scan), which has no such limits.  Which pipeline a sweep runs is a function of its labels.
 // ---------------------------------------------------------------------------------------
 constexpr int kCHMax = 64;       // poses per chunk: 64, 32 or 16 (lane p holds pose p's header); short
                                  // sequences use short chunks -- a chunk is ONE wave's serial work
@@ -1851,8 +1852,8 @@ __global__ __launch_bounds__(kBlock) void k_chunk_l1(const double* __restrict__ 
                 // One buffer descriptor per array spans exactly this pose's np entries: the hardware drops the stores of the
                 // lanes beyond it (raw buffer addressing, offset >= range) -- no branch around the stores, so the compiler
                 // still counts them exactly, and no idle-lane traffic at all.
-                // (beams of the landmark inside the chunk through this pose -- exact; at most 64 poses x 8192 beams < 2^24,
-                // both bounds checked at upload -- and, in the low byte, the slot of the entry's record: one word)
+                // (beams of the landmark inside the chunk through this pose -- exact; at most 64 poses x ICM_MAX_BEAMS = 1462
+                // beams < 2^24, both bounds checked at upload -- and, in the low byte, the slot of the entry's record: one word)
                 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
                 const int off8 = lane << 3;
                 __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, ax), __builtin_amdgcn_make_buffer_rsrc(pre_x + ep, 0, np << 3, kRawBuffer), off8, 0, 0);

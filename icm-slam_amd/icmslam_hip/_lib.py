@@ -111,6 +111,7 @@ SIGNATURES = {
     "icm_get_fused_deferred": (C.c_int, [_H, _lp]),
     "icm_set_entry_path": (C.c_int, [_H, C.c_int]),
     "icm_get_entry_path": (C.c_int, [_H]),
+    "icm_get_entry_layout": (C.c_int, [_H, _ip]),
     "icm_set_energy_form": (C.c_int, [_H, C.c_int]),
     "icm_version": (C.c_char_p, []),
     "icm_build_id": (C.c_char_p, []),

@@ -558,6 +558,13 @@ class SweepEngine:
         """Pipeline the last sweep ran: 'hier' or 'sort'."""
         return "hier" if self.lib.icm_get_entry_path(self.h) == 1 else "sort"
 
+    def entry_layout(self):
+        """Layout of the hierarchical pipeline: dict(chunk_poses, chunk_group, nsuper, nchunks, scan_ran) -- scan_ran:
+        whether the last sweep ran the scan kernels."""
+        a = np.zeros(5, dtype=np.int32)
+        self._chk(self.lib.icm_get_entry_layout(self.h, iptr(a)))
+        return dict(chunk_poses=int(a[0]), chunk_group=int(a[1]), nsuper=int(a[2]), nchunks=int(a[3]), scan_ran=bool(a[4]))
+
     def set_gpu_filtrar(self, on):
         self._chk(self.lib.icm_set_gpu_filtrar(self.h, int(bool(on))))
 

@@ -119,14 +119,22 @@ int icm_staging_layout(int64_t nnz, int64_t nloc, int64_t *out3);
 /* Pipeline that turns the per-pose entries into running-mean targets (the time-ordered
  * per-landmark prefix of Mapa.actualizar, scripts/ICM_SLAM_tools.py:184-196):
  *   1 / -1 (default) = hierarchical running sums (pose chunks -> superchunks -> per-landmark
- *       column prefix; no sort); used for the moment-form solves.  A map so dense that a
- *       64-pose chunk sees more than ~190 distinct landmarks makes the sweep fall back to
+ *       column prefix; no sort); used for the moment-form solves.  The sweep falls back to
+ *       the sort-based pipeline exactly when a pose has more than 64 entries (distinct labels),
+ *       a chunk more than 224 (kT1 - 32) distinct labels or a superchunk more than 1536 (kT2Cap),
+ *       fresh labels of landmark-creating poses included, and stays on it until icm_set_state;
  *   0 = the sort-based pipeline (radix sort of the entries by landmark + one wave per
  *       landmark), which has no such limit and also serves energy forms 1/2 and icm_set_debug.
  * The two differ only in the order the per-landmark sums are added up (~1e-15 relative).
  * icm_get_entry_path: pipeline the last sweep actually ran (0 or 1). */
 int icm_set_entry_path(icm_handle *h, int mode);
 int icm_get_entry_path(const icm_handle *h);
+
+/* Layout of the hierarchical pipeline for the uploaded shard of nloc poses (host values, no GPU work): out5 = [poses
+ * per chunk CH (16 below 16384 poses, 32 below 65536, else 64), chunks per superchunk G = ceil(nchunks / 64),
+ * superchunks = ceil(nchunks / G), chunks = ceil(nloc / CH), 1 if the last sweep ran the scan kernels (a sweep queued
+ * whole after the first leaves them out)].  ICM_ERR_ARG before icm_upload. */
+int icm_get_entry_layout(const icm_handle *h, int32_t *out5);
 
 /* Where Mapa.filtrar runs inside a sweep: 1 (default) = on the GPU (the k_fl_* kernel chain on a
  * side stream: prune, grid, nearest-neighbour pairs, and -- when survivors are closer than dist_thr

@@ -122,14 +122,30 @@ def test_dense_map_falls_back_to_sort_based_pipeline():
 
 
 def test_many_landmarks_per_chunk_still_hierarchical_or_falls_back_consistently():
-    """A field dense enough that 64 consecutive poses see close to the chunk table's capacity:
-    whichever pipeline the sweep ends up on, the result equals the sort-based one."""
+    """A field dense enough that a chunk of consecutive poses sees many distinct landmarks: the
+    pipeline the sweeps end up on is the one the fallback rule gives for the C oracle's labels of
+    both sweeps (phase_b_shapes.expected_path; an overflow keeps the handle on the sort-based
+    pipeline), and the result equals the sort-based one."""
     from ICM_SLAM_tools import ConfigICM
     from icmslam_hip import SweepEngine
     from icmslam_hip.synthetic import make_workload
+    from oracle import c_oracle as co
+    import phase_b_shapes as pb
     wl = make_workload(1350, 400, 360)   # one lane through a 50 m field, ends inside it
     d = dict(wl.config)
     cfg = ConfigICM(D=d)
+    kept = co.prefilter(cfg, wl.scans.T)
+    xc, mv, la = wl.x_init.copy(), wl.map_init, wl.map_init.shape[1]
+    want = "hier"
+    for _ in range(2):
+        a = {}
+        like = type("Labels", (), dict(map=mv, T=wl.T))
+        mv, _, la, _ = co.sweep(cfg, kept, wl.u, wl.odometry, wl.x0, mv, xc, la, "redblack", assoc=a)
+        r = pb.reach(like, kept[0], a["labels"])
+        print("oracle: entries per pose <= %d, labels per chunk <= %d, per superchunk <= %d"
+              % (r["entries"].max(), r["per_chunk"].max(), r["per_super"].max()))
+        if pb.expected_path(r) == "sort":
+            want = "sort"
     out = {}
     for mode in ("sort", "auto"):
         eng = SweepEngine(cfg)
@@ -142,7 +158,8 @@ def test_many_landmarks_per_chunk_still_hierarchical_or_falls_back_consistently(
         eng.close()
     (xs, ms, cs, Ks), _ = out["sort"]
     (xh, mh, ch, Kh), path = out["auto"]
-    print("pipeline used:", path)
+    print("pipeline used:", path, "expected:", want)
+    assert path == want
     assert Ks == Kh and np.array_equal(cs, ch) and np.abs(ms - mh).max() <= 1e-11
     dd = np.abs(xs - xh).max(axis=0)
     assert dd.max() <= 1e-9

@@ -110,3 +110,12 @@ def check_runs(eng, thr):
     full = k[np.flatnonzero(f > 0) - 1] == 64
     assert ((g_ > gap * (1 - 1e-12)) | (e_ > ext * (1 - 1e-12)) | full).all()
     return n_runs, float(k.mean()), float(r.max())
+
+
+def entry_layout(nloc):
+    """The host's layout of the hierarchical entry pipeline for a shard of nloc poses (icm_prefilter; kMaxSuper = 64
+    matrix rows): poses per chunk, chunks per superchunk, superchunks, chunks."""
+    ch = 64 if nloc >= 65536 else (32 if nloc >= 16384 else 16)
+    nchunks = (nloc + ch - 1) // ch
+    g = (nchunks + 63) // 64
+    return dict(chunk_poses=ch, chunk_group=g, nsuper=(nchunks + g - 1) // g, nchunks=nchunks)
