@@ -189,7 +189,6 @@ struct icm_handle {
     bool brute = false, debug = false, per_beam = false, assoc_kept = false;
     double thr2 = 0.0;  // largest s with sqrt(s) <= dist_thr
     int hash_slots = 128;  // phase A's per-pose label table; grows to 256 on overflow
-    int solve_quad = -1;   // -1 automatic, 0 one lane per pose, 1 one quad per pose
     int form = 0;  // 0 moments (lane per pose), 1 per beam, 2 per entry (wave per pose)
     int *pin_i = nullptr, *pin_i_dev = nullptr;   // pinned host words and their device-side address
     double* pin_d = nullptr;  // pinned staging: raw map download (3L)
@@ -214,7 +213,6 @@ struct icm_handle {
     hipEvent_t ev_ph[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     double ph_ms[5] = {0, 0, 0, 0, 0};   // local | exchange (+ waiting for the slowest rank) | targets | solve | host time in finish
     int64_t ph_n = 0;
-    int solve_ppw = 0;   // poses per wave of the one-launch solve: 0 automatic, 32 or 64 (ICM_SOLVE_PPW)
     int fault = 0;   // test hook (icm_set_fault): 1 = the next icm_sweep_local reports a HIP error, 2 = the next icm_sweep_targets does (behind the exchange)
     int64_t dropin_counts[3] = {0, 0, 0};   // icm_sweep calls: [0] started without an upload, [1] of those: the check failed (started over), [2] poses mirrored into the caller's array
     double h_x0[3] = {0, 0, 0};      // host copy of x0 as uploaded
@@ -421,7 +419,6 @@ int icm_create(const icm_config* cfg, int device, icm_handle** out) {
         h->thr2 = s2;
     }
     if (const char* ev = std::getenv("ICM_L3_EVENT")) h->l3_spin = std::atoi(ev) == 0;
-    if (const char* ev = std::getenv("ICM_SOLVE_PPW")) h->solve_ppw = std::atoi(ev);
     h->own_stream = true;
     h->h_counts.assign((size_t)cfg->L, 0.0);
     *out = h;
@@ -1500,9 +1497,8 @@ static SolveSeg shard_segment(const icm_handle* h, const int* abort) {
 static int launch_fused_solve(icm_handle* h, SolveArgs a, SolveSeg g, hipStream_t st) {
     const int64_t npc = (g.t1 - g.t0) / 2 + 1;   // poses per colour (upper bound)
     // poses per wave: 64, or 32 while both colours' half-filled waves still find a SIMD each twice over (S1, the shards of
-    // an 8-rank job): a wave lasts as long as its slowest lane (ICM_SOLVE_PPW: A/B runs)
-    int ppw = (4 * (int64_t)((npc + 31) / 32) <= 4 * (int64_t)h->cu_count) ? 32 : kWave;
-    if (h->solve_ppw == 32 || h->solve_ppw == 64) ppw = h->solve_ppw;
+    // an 8-rank job): a wave lasts as long as its slowest lane
+    const int ppw = (4 * (int64_t)((npc + 31) / 32) <= 4 * (int64_t)h->cu_count) ? 32 : kWave;
     const int nwv = (int)((npc + ppw - 1) / ppw);
     if (h->solve_flag_waves < nwv) {
         HIPCHK(h, hipStreamSynchronize(h->stream));   // (re-allocation: nothing may still be polling the old flags)
@@ -1581,14 +1577,11 @@ int icm_sweep_solve(icm_handle* h, int schedule, int colour) {
         else {
             const bool iso = h->cfg.Q[0] == h->cfg.Q[1] && h->cfg.R[0] == h->cfg.R[1];
             const bool fold = h->fold_mode < 0 ? iso : h->fold_mode == 1;
-            if (h->solve_quad == 1) {   // (icm_set_solve_lanes(1): the quad form of the chain, a cross-check)
-                if (fold) TIMED(h, KID_SOLVE, (k_solve_m_sequential<true, true><<<1, kWave, 0, h->stream>>>(a)));
-                else TIMED(h, KID_SOLVE, (k_solve_m_sequential<false, true><<<1, kWave, 0, h->stream>>>(a)));
-            } else if (fold) TIMED(h, KID_SOLVE, (k_solve_m_sequential<true><<<1, kWave, 0, h->stream>>>(a)));
+            if (fold) TIMED(h, KID_SOLVE, (k_solve_m_sequential<true><<<1, kWave, 0, h->stream>>>(a)));
             else TIMED(h, KID_SOLVE, (k_solve_m_sequential<false><<<1, kWave, 0, h->stream>>>(a)));
             h->rot_valid = false;   // (the chain does not keep the rotation pairs: k_pose_rot at the head of the next sweep)
         }
-    } else if (schedule == ICM_SCHEDULE_REDBLACK && colour < 0 && h->form == 0 && h->fuse_colours && h->solve_quad != 1) {
+    } else if (schedule == ICM_SCHEDULE_REDBLACK && colour < 0 && h->form == 0 && h->fuse_colours) {
         // both colours in one launch, even waves chase the odd ones (a shard: its ghost pose is the first odd pose)
         int rc = launch_fused_solve(h, a, shard_segment(h, abort), h->stream);
         if (rc) return rc;
@@ -1597,19 +1590,10 @@ int icm_sweep_solve(icm_handle* h, int schedule, int colour) {
         const int nw = (g.t1 - g.t0) / 2 + 1;
         for (int col = 1; col >= 0; --col) {
             if (!(colour == col || colour < 0)) continue;
+            // moment form: one lane per pose, 64 poses per wave (one DPP quad per pose measured slower: DESIGN.md §5)
             if (h->form == 1) TIMED(h, KID_SOLVE, (k_solve_colour<true><<<nblocks_waves(nw), kBlock, 0, h->stream>>>(a, col)));
             else if (h->form == 2) TIMED(h, KID_SOLVE, (k_solve_colour<false><<<nblocks_waves(nw), kBlock, 0, h->stream>>>(a, col)));
-            else {
-                // Throughput form: one lane per pose (64 poses per wave).  Latency form: one DPP quad
-                // per pose evaluating the four candidate points of an iteration at once.
-                // With the folded energy an evaluation is a sixth of an iteration's instructions, so the quad's
-                // one-evaluation iteration no longer pays for its broadcasts: the lane form is faster at every
-                // size measured (S1: 0.122 against 0.157 ms, 600 poses: 0.099 against 0.115) and is the
-                // automatic choice; the quad form stays selectable (icm_set_solve_lanes) and bit-identical.
-                const bool quad = h->solve_quad == 1;
-                if (quad) TIMED(h, KID_SOLVE, (k_solve_mq_colour<<<nblocks_threads((int64_t)nw * 4), kBlock, 0, h->stream>>>(a, g, col)));
-                else TIMED(h, KID_SOLVE, (k_solve_m_colour<<<nblocks_waves((nw + kWave - 1) / kWave), kBlock, 0, h->stream>>>(a, g, col)));
-            }
+            else TIMED(h, KID_SOLVE, (k_solve_m_colour<<<nblocks_waves((nw + kWave - 1) / kWave), kBlock, 0, h->stream>>>(a, g, col)));
         }
     } else {
         FAIL(h, ICM_ERR_ARG, "icm_sweep_solve: unknown schedule");
@@ -2570,13 +2554,6 @@ int icm_set_energy_form(icm_handle* h, int form) {
     if (form < 0 || form > 2) FAIL(h, ICM_ERR_ARG, "icm_set_energy_form: form must be 0, 1 or 2");
     h->form = form;
     h->per_beam = form == 1;
-    return ICM_OK;
-}
-
-int icm_set_solve_lanes(icm_handle* h, int mode) {
-    if (!h) return ICM_ERR_ARG;
-    if (mode < -1 || mode > 1) FAIL(h, ICM_ERR_ARG, "icm_set_solve_lanes: mode must be -1, 0 or 1");
-    h->solve_quad = mode;
     return ICM_OK;
 }
 

@@ -31,12 +31,6 @@ __device__ __forceinline__ double wrap_pi(double a) {
     return r;
 }
 
-__device__ __forceinline__ double bcast_first(double v) {
-    int lo = __builtin_amdgcn_readfirstlane(__double2loint(v));
-    int hi = __builtin_amdgcn_readfirstlane(__double2hiint(v));
-    return __hiloint2double(hi, lo);
-}
-
 // DPP move of a double (two dwords); lanes without a source read 0.  With every row enabled the
 // zero comes from bound_ctrl (no destination to preset: saves a v_mov per dword); with masked rows
 // (row_bcast into rows 1/3 or 2/3) the disabled rows keep the preset 0.
@@ -186,7 +180,7 @@ constexpr int kMomentCount = 14;
 
 // The moment-form energy is the build's own arithmetic -- an exact regrouping of the reference's
 // per-beam sum, not its expression tree -- so it may use fused multiply-adds.  They are written
-// out (fma_) instead of left to `fp contract`: every kernel form (lane, quad, sequential,
+// out (fma_) instead of left to `fp contract`: every kernel form (one-launch, per-colour, sequential,
 // fast and generic path) then rounds identically by construction.
 // The three-operand VOP3 form is spelled out: left to itself hipcc selects the destructive
 // two-operand v_fmac_f64 and then has to copy every loop-invariant addend (polynomial
@@ -740,135 +734,6 @@ __device__ __forceinline__ bool nelder_mead3(F f, double sx, double sy, double s
         stopped = stop();
         // (it < maxiter needs no test of its own: every iteration costs at least one evaluation, so nfev >= it + 3, and
         // the two budgets are the same number)
-        static_assert(maxfun <= maxiter + 3, "the evaluation budget implies the iteration budget");
-        go = !aborted & (nfev < maxfun) & !(settled() | stopped);
-    }
-    out[0] = v0.x; out[1] = v0.y; out[2] = v0.t; out[3] = v0.f;
-    out[4] = (double)it; out[5] = (double)nfev;
-    return stopped;
-}
-
-// ---------------------------------------------------------------------------------------
-// Latency form of the same Nelder-Mead: FOUR lanes (one DPP quad) per pose.  The reflection,
-// expansion, outside and inside contraction points of an iteration depend only on the centroid
-// and the worst vertex, so the quad evaluates all four at once (lane r evaluates point r) and
-// then takes SciPy's decision from the four values; the three shrink vertices and the four
-// initial vertices are evaluated in parallel the same way.  An iteration then costs ONE energy
-// evaluation of latency instead of up to two (shrink: one instead of three), at four times the
-// arithmetic -- the right trade when there are fewer poses than lanes to fill (small shards,
-// the sequential schedule).  Same arithmetic per point, same decisions, same nfev accounting
-// (only logically evaluated points are counted, maxfun aborts as in the scalar form), so the
-// result is bit-identical to nelder_mead3.
-// ---------------------------------------------------------------------------------------
-template <int K>
-__device__ __forceinline__ double quad_bcast(double v) {  // value of lane K of the quad, in all four lanes
-    constexpr int ctrl = K | (K << 2) | (K << 4) | (K << 6);  // quad_perm:[K,K,K,K]
-    int sl = __double2loint(v), sh = __double2hiint(v);
-    asm("" : "+v"(sl), "+v"(sh));   // (a DPP source is a vector register, also where the value happens to be wave-uniform: k_init_pass)
-    const int lo = __builtin_amdgcn_update_dpp(0, sl, ctrl, 0xF, 0xF, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, sh, ctrl, 0xF, 0xF, false);
-    return __hiloint2double(hi, lo);
-}
-
-// true in all four lanes of a DPP quad when it holds in one of them
-__device__ __forceinline__ bool quad_any(bool b) {
-    int v = b ? 1 : 0;
-    asm("" : "+v"(v));
-    v |= __builtin_amdgcn_mov_dpp(v, 0xB1, 0xF, 0xF, true);   // quad_perm:[1,0,3,2]
-    v |= __builtin_amdgcn_mov_dpp(v, 0x4E, 0xF, 0xF, true);   // quad_perm:[2,3,0,1]
-    return v != 0;
-}
-
-template <class F, class S = NeverStop>
-__device__ __forceinline__ bool nelder_mead3_quad(F f, double sx, double sy, double st, int role, double out[6], S stop = S()) {
-    // Written like nelder_mead3: one straight-line iteration with predicates, ONE evaluation call site in the loop (lane
-    // `role` of the quad evaluates point `role`: reflection, expansion, outside, inside contraction), the shrink a rarely
-    // entered block, one loop condition at the bottom.  `stop` must be quad-uniform (the caller folds it over the quad).
-    constexpr int maxfun = 600, maxiter = 600;
-    const double xatol = 1e-3, fatol = 1e-4;
-    const double grow = 1 + 0.05;
-    Vtx v0{sx, sy, st, 0.0};
-    Vtx v1{sx != 0.0 ? grow * sx : 0.00025, sy, st, 0.0};
-    Vtx v2{sx, sy != 0.0 ? grow * sy : 0.00025, st, 0.0};
-    Vtx v3{sx, sy, st != 0.0 ? grow * st : 0.00025, 0.0};
-    {
-        Vtx c = v0;
-        if (role == 1) c = v1;
-        if (role == 2) c = v2;
-        if (role == 3) c = v3;
-        const double fv = f(c.x, c.y, c.t);
-        v0.f = quad_bcast<0>(fv);
-        v1.f = quad_bcast<1>(fv);
-        v2.f = quad_bcast<2>(fv);
-        v3.f = quad_bcast<3>(fv);
-    }
-    int nfev = 4, it = 1;
-    sort4(v0, v1, v2, v3);
-    // point `role` of an iteration = ca xbar + cb sim[-1]: (2, -1), (3, -2), (1.5, -0.5), (0.5, 0.5); cb sim[-1] is exact,
-    // so fma(cb, x_w, ca xbar) rounds like the scalar form's reflection 2 xbar - x_w and its second point
-    const double ca = role == 0 ? 2.0 : (role == 1 ? 3.0 : (role == 2 ? 1.5 : 0.5));
-    const double cb = role == 0 ? -1.0 : (role == 1 ? -2.0 : (role == 2 ? -0.5 : 0.5));
-    auto settled = [&]() {
-        const double dx = fmax(fmax(amax3(v1, v0), amax3(v2, v0)), amax3(v3, v0));
-        const double df = fmax(fmax(fabs(v0.f - v1.f), fabs(v0.f - v2.f)), fabs(v0.f - v3.f));
-        return (dx <= xatol) & (df <= fatol);
-    };
-    bool stopped = stop();
-    bool go = !(settled() | stopped);
-    while (go) {
-        const double bx = div3((v0.x + v1.x) + v2.x);
-        const double by = div3((v0.y + v1.y) + v2.y);
-        const double bt = div3((v0.t + v1.t) + v2.t);
-        const double mx = fma_(cb, v3.x, ca * bx), my = fma_(cb, v3.y, ca * by), mt = fma_(cb, v3.t, ca * bt);
-        const double fm = f(mx, my, mt);
-        Vtx r{quad_bcast<0>(mx), quad_bcast<0>(my), quad_bcast<0>(mt), quad_bcast<0>(fm)};
-        ++nfev;
-        const bool lt0 = r.f < v0.f, lt2 = r.f < v2.f, lt3 = r.f < v3.f;
-        const bool need2 = lt0 | !lt2;
-        const bool can2 = need2 & (nfev < maxfun);
-        // the second point: expansion (lane 1), outside (lane 2) or inside (lane 3) contraction
-        const double e1x = quad_bcast<1>(mx), e1y = quad_bcast<1>(my), e1t = quad_bcast<1>(mt), e1f = quad_bcast<1>(fm);
-        const double e2x = quad_bcast<2>(mx), e2y = quad_bcast<2>(my), e2t = quad_bcast<2>(mt), e2f = quad_bcast<2>(fm);
-        const double e3x = quad_bcast<3>(mx), e3y = quad_bcast<3>(my), e3t = quad_bcast<3>(mt), e3f = quad_bcast<3>(fm);
-        Vtx t{lt0 ? e1x : (lt3 ? e2x : e3x), lt0 ? e1y : (lt3 ? e2y : e3y), lt0 ? e1t : (lt3 ? e2t : e3t), lt0 ? e1f : (lt3 ? e2f : e3f)};
-        nfev += can2 ? 1 : 0;
-        const bool t_lt_r = t.f < r.f, t_le_r = t.f <= r.f, t_lt_w = t.f < v3.f;
-        const bool take_t = (lt0 & t_lt_r) | (!lt0 & lt3 & t_le_r) | (!lt3 & t_lt_w);
-        const bool shrink = can2 & !lt0 & !take_t;
-        const bool aborted0 = need2 & !can2;
-        const bool use_t = can2 & take_t;
-        const bool keep = shrink | aborted0;
-        insert_vertex(v0, v1, v2, v3, r, t, use_t, !keep);
-        bool aborted = aborted0;
-        if (__builtin_expect(shrink, 0)) {
-            // sim[j] = sim[0] + sigma (sim[j] - sim[0]), j = 1..3, each followed by its evaluation; a call beyond maxfun
-            // aborts after the vertex was moved (SciPy's order)
-            const int room = maxfun - nfev;
-            Vtx n1 = v1, n2 = v2, n3 = v3;
-            n1.x = v0.x + 0.5 * (v1.x - v0.x); n1.y = v0.y + 0.5 * (v1.y - v0.y); n1.t = v0.t + 0.5 * (v1.t - v0.t);
-            n2.x = v0.x + 0.5 * (v2.x - v0.x); n2.y = v0.y + 0.5 * (v2.y - v0.y); n2.t = v0.t + 0.5 * (v2.t - v0.t);
-            n3.x = v0.x + 0.5 * (v3.x - v0.x); n3.y = v0.y + 0.5 * (v3.y - v0.y); n3.t = v0.t + 0.5 * (v3.t - v0.t);
-            Vtx c = n1;
-            if (role == 2) c = n2;
-            if (role == 3) c = n3;
-            const double fs = f(c.x, c.y, c.t);
-            n1.f = quad_bcast<1>(fs);
-            n2.f = quad_bcast<2>(fs);
-            n3.f = quad_bcast<3>(fs);
-            if (room >= 3) {
-                v1 = n1; v2 = n2; v3 = n3;
-                nfev += 3;
-            } else {  // vertex `room + 1` is moved but not evaluated, later ones are untouched
-                aborted = true;
-                if (room >= 1) v1 = n1; else { v1.x = n1.x; v1.y = n1.y; v1.t = n1.t; }
-                if (room >= 2) v2 = n2; else if (room == 1) { v2.x = n2.x; v2.y = n2.y; v2.t = n2.t; }
-                if (room == 2) { v3.x = n3.x; v3.y = n3.y; v3.t = n3.t; }
-                nfev += room > 0 ? room : 0;
-            }
-            sort4(v0, v1, v2, v3);
-        }
-        it += aborted ? 0 : 1;
-        stopped = stop();
         static_assert(maxfun <= maxiter + 3, "the evaluation budget implies the iteration budget");
         go = !aborted & (nfev < maxfun) & !(settled() | stopped);
     }

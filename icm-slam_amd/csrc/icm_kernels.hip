@@ -2934,7 +2934,7 @@ __global__ __launch_bounds__(kWave) void k_ghost_moments(const double* __restric
     }
 }
 
-// One LANE (QUAD: one DPP quad, role = lane & 3) solves pose tg with the moment-form energy.
+// One LANE solves pose tg with the moment-form energy (the DPP-quad form measured slower and was removed: DESIGN.md §5).
 // `prev` = x[:,tg-1] as it stands now.
 // Everything a pose solve reads that the launch it runs in does not write: loaded BEFORE an even wave of the one-launch
 // solve starts to wait for its odd neighbours, so that what is left behind the wait is the two neighbour poses, one
@@ -2977,9 +2977,9 @@ __device__ __forceinline__ void load_pose_in(const SolveArgs& a, int tg, PoseIn&
 // solve with FOLD = false (folded where valid, term by term elsewhere).
 // prev = x[:, tg-1] as it stands now; prev_in_table: its (cos, sin) are in the cs table (it was written before this
 // launch began) -- else they are formed here.
-template <bool QUAD, bool FOLD = false>
+template <bool FOLD = false>
 __device__ __forceinline__ bool solve_pose_in(const SolveArgs& a, int tg, const PoseIn& in, const double prev[3], bool prev_in_table,
-                                              double& r0, double& r1, double& r2, int role = 0) {
+                                              double& r0, double& r1, double& r2) {
     const bool last = tg + 1 >= a.T;
     if (in.n == 0) {  // no beams (scripts/ICM_ROS.py:143-147)
         const double* nx = a.x + 3 * (size_t)(tg + 1);
@@ -3030,20 +3030,13 @@ __device__ __forceinline__ bool solve_pose_in(const SolveArgs& a, int tg, const 
             left |= !ok;
             return e;
         };
-        if (QUAD) {   // (any of the quad's four points: a point the iteration discards may ask for the second solve too -- same result)
-            auto stopq = [&]() { const bool l = quad_any(left); left = false; return l; };
-            if (nelder_mead3_quad(ef, sx, sy, st, role, out, stopq)) return false;
-        } else {
-            auto stop = [&]() { const bool l = left; left = false; return l; };
-            if (nelder_mead3(ef, sx, sy, st, out, stop)) return false;
-        }
-    } else if (QUAD) {
-        nelder_mead3_quad([&](double px, double py, double th) { return pose_energy_moments(c, m, f, px, py, th); }, sx, sy, st, role, out);
+        auto stop = [&]() { const bool l = left; left = false; return l; };
+        if (nelder_mead3(ef, sx, sy, st, out, stop)) return false;
     } else {
         nelder_mead3([&](double px, double py, double th) { return pose_energy_moments(c, m, f, px, py, th); }, sx, sy, st, out);
     }
     r0 = out[0]; r1 = out[1]; r2 = out[2];
-    if (a.diag && role == 0) {
+    if (a.diag) {
         a.diag[3 * (size_t)tg] = out[3];
         a.diag[3 * (size_t)tg + 1] = out[4];
         a.diag[3 * (size_t)tg + 2] = out[5];
@@ -3052,12 +3045,11 @@ __device__ __forceinline__ bool solve_pose_in(const SolveArgs& a, int tg, const 
 }
 
 // load + solve in one go (the launches in which nothing waits between the two)
-template <bool QUAD, bool FOLD = false>
-__device__ __forceinline__ bool solve_pose_moments(const SolveArgs& a, int tg, const double prev[3], bool prev_in_table, double res[3],
-                                                   int role = 0) {
+template <bool FOLD = false>
+__device__ __forceinline__ bool solve_pose_moments(const SolveArgs& a, int tg, const double prev[3], bool prev_in_table, double res[3]) {
     PoseIn in;
     load_pose_in(a, tg, in);
-    return solve_pose_in<QUAD, FOLD>(a, tg, in, prev, prev_in_table, res[0], res[1], res[2], role);
+    return solve_pose_in<FOLD>(a, tg, in, prev, prev_in_table, res[0], res[1], res[2]);
 }
 
 // A time segment of the sequence solved by one launch: poses [t0, t1).  shift = 0 for the segment
@@ -3095,7 +3087,7 @@ __global__ __launch_bounds__(kBlock) void k_solve_m_colour(SolveArgs a, SolveSeg
     if (tg >= g.t1) return;
     double prev[3] = {a.x[3 * (size_t)(tg - 1)], a.x[3 * (size_t)(tg - 1) + 1], a.x[3 * (size_t)(tg - 1) + 2]};
     double res[3];
-    solve_pose_moments<false>(a, tg, prev, true, res);   // (prev was written before this launch began: its pair is in the table)
+    solve_pose_moments(a, tg, prev, true, res);   // (prev was written before this launch began: its pair is in the table)
     store_pose(a, tg, res, false);
 }
 
@@ -3210,7 +3202,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(2))) voi
         double prev[3] = {a.x[3 * (size_t)(tg - 1)], a.x[3 * (size_t)(tg - 1) + 1], a.x[3 * (size_t)(tg - 1) + 2]};
         // an odd pose's lower neighbour is an OLD even pose (its pair is in the table); an even pose's was written a
         // moment ago by an odd wave of this launch, which publishes the pose, not the pair
-        redo = !solve_pose_in<false, true>(a, tg, in, prev, !even, r0, r1, r2);   // (false: an evaluation left the folded form's range)
+        redo = !solve_pose_in<true>(a, tg, in, prev, !even, r0, r1, r2);   // (false: an evaluation left the folded form's range)
     }
     // The complete-energy solve, everything reloaded from memory (tgc is opaque to the compiler, so nothing of it is
     // shared with -- kept alive across -- the folded loop above).  First pass: this wave's own poses (FOLD: the rare ones
@@ -3226,7 +3218,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(2))) voi
             if (redo) {
                 double prev[3] = {a.x[3 * (size_t)(tgc - 1)], a.x[3 * (size_t)(tgc - 1) + 1], a.x[3 * (size_t)(tgc - 1) + 2]};
                 double res[3];
-                solve_pose_moments<false, false>(a, tgc, prev, prev_tab, res);
+                solve_pose_moments(a, tgc, prev, prev_tab, res);
                 r0 = res[0]; r1 = res[1]; r2 = res[2];
             }
             if (FOLD && first && lane == (int)__builtin_ctzll(mredo)) atomicAdd(&counts[1], (unsigned long long)__popcll(mredo));
@@ -3288,38 +3280,17 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(2))) voi
     }
 }
 
-// The same half sweep in latency form: one DPP quad (4 lanes) per pose, 16 poses per wave
-// (nelder_mead3_quad).
-__global__ __launch_bounds__(kBlock) void k_solve_mq_colour(SolveArgs a, SolveSeg g, int colour) {
-    if (seg_aborted(g)) return;
-    const int gid = blockIdx.x * kBlock + threadIdx.x;
-    const int j = gid >> 2, role = gid & 3;
-    const int tg = seg_pose(g, colour == 0, j);
-    if (tg >= g.t1) return;  // whole quads leave together
-    double prev[3] = {a.x[3 * (size_t)(tg - 1)], a.x[3 * (size_t)(tg - 1) + 1], a.x[3 * (size_t)(tg - 1) + 2]};
-    double res[3];
-    solve_pose_moments<true>(a, tg, prev, true, res, role);
-    if (role == 0) store_pose(a, tg, res, false);
-}
-
 // Reference order (scripts/ICM_ROS.py:141: t = 1 .. T-1, every pose from its just-solved predecessor), moment form.
-// Round 4: ONE lane walks the chain (the quad form's broadcasts no longer pay since the folded energy: an evaluation is
-// a sixth of an iteration).  The inputs of pose t + 1 that do not depend on pose t's result (moment sums, odometry,
+// ONE lane walks the chain.  The inputs of pose t + 1 that do not depend on pose t's result (moment sums, odometry,
 // controls, its own previous value) are requested before pose t is solved; the Nelder-Mead loop evaluates the folded
 // energy only (FOLD: isotropic weights) and a pose that leaves its range is solved once more with the complete energy;
 // the rotation pairs kept beside the poses are NOT written here -- two generic sincos per pose on a chain of T - 1
 // solves -- but by k_pose_rot at the head of the next sweep, in parallel (the host clears rot_valid).  data_IJAC2018:
-// 53 -> ?? ms per sweep; the same arithmetic per pose as every other solve form (bit-identical).
-// Round 5 measured the chain walked by ONE DPP QUAD (QUAD = true: nelder_mead3_quad, the four candidate points of an
-// iteration evaluated at once, lane r point r, the folded energy in the loop -- one evaluation of latency per iteration
-// instead of two): 45.2 against 43.1 ms on data_IJAC2018, and 55.3 against 50.6 ms for k_init_pass.  The folded energy
-// is ~40 of an iteration's ~210 instructions; what the chain costs is the Nelder-Mead's bookkeeping, which the quad does
-// not shorten (it adds the exchanges), at one dependent instruction per ~4.6 cycles of a lone wave.  Kept as a
-// cross-check (bit-identical), the lane form is what runs.
-template <bool FOLD, bool QUAD = false>
+// 53 -> ?? ms per sweep; the same arithmetic per pose as every other solve form (bit-identical).  (One DPP quad per
+// pose, the four candidate points of an iteration at once, measured slower and was removed: DESIGN.md §5.)
+template <bool FOLD>
 __global__ __launch_bounds__(kWave) void k_solve_m_sequential(SolveArgs a) {
-    if (threadIdx.x >= (QUAD ? 4 : 1)) return;
-    const int role = threadIdx.x;
+    if (threadIdx.x >= 1) return;
     double prev[3] = {a.x[0], a.x[1], a.x[2]};
     if constexpr (!FOLD) {
         // the complete energy in the loop (anisotropic weights; a cross-check otherwise): load and solve, no prefetch -- with
@@ -3327,8 +3298,8 @@ __global__ __launch_bounds__(kWave) void k_solve_m_sequential(SolveArgs a) {
         // and its null check does not assemble on gfx950
         for (int tg = 1; tg < a.T; ++tg) {
             double res[3];
-            solve_pose_moments<QUAD, false>(a, tg, prev, false, res, role);
-            if (role == 0) store_pose_xyz(a, tg, res, false);
+            solve_pose_moments(a, tg, prev, false, res);
+            store_pose_xyz(a, tg, res, false);
             prev[0] = res[0]; prev[1] = res[1]; prev[2] = res[2];
         }
         return;
@@ -3341,16 +3312,16 @@ __global__ __launch_bounds__(kWave) void k_solve_m_sequential(SolveArgs a) {
         nxt.n = 0;
         if (tg + 1 < a.T) load_pose_in(a, tg + 1, nxt);
         double r0 = 0.0, r1 = 0.0, r2 = 0.0;
-        bool ok = solve_pose_in<QUAD, FOLD>(a, tg, cur, prev, false, r0, r1, r2, role);   // (prev is the pose this lane / quad has just solved: its pair is formed here)
+        bool ok = solve_pose_in<FOLD>(a, tg, cur, prev, false, r0, r1, r2);   // (prev is the pose this lane has just solved: its pair is formed here)
         if (FOLD && !ok) {
             int tgc = tg;
             asm volatile("" : "+v"(tgc));
             double res[3];
-            solve_pose_moments<QUAD, false>(a, tgc, prev, false, res, role);
+            solve_pose_moments(a, tgc, prev, false, res);
             r0 = res[0]; r1 = res[1]; r2 = res[2];
         }
         const double res[3] = {r0, r1, r2};
-        if (role == 0) store_pose_xyz(a, tg, res, false);
+        store_pose_xyz(a, tg, res, false);
         prev[0] = r0; prev[1] = r1; prev[2] = r2;
         cur = nxt;
     }
@@ -3533,9 +3504,8 @@ __global__ __launch_bounds__(kWave) void k_init_pass(InitArgs a) {
             double r0 = 0.0, r1 = 0.0, r2 = 0.0;
             const bool iso = a.Q0 == a.Q1 && a.R0 == a.R1;
             bool ok = false;
-            // (the quad form here -- every DPP quad of the wave on the same numbers -- measured 55.3 against 50.6 ms: k_solve_m_sequential)
-            if (iso) ok = solve_pose_in<false, true>(sa, t, in, xt, false, r0, r1, r2);
-            if (!ok) solve_pose_in<false, false>(sa, t, in, xt, false, r0, r1, r2);
+            if (iso) ok = solve_pose_in<true>(sa, t, in, xt, false, r0, r1, r2);
+            if (!ok) solve_pose_in<false>(sa, t, in, xt, false, r0, r1, r2);
             xt[0] = r0; xt[1] = r1; xt[2] = r2;
         }
         if (lane == 0) {

@@ -505,10 +505,6 @@ class SweepEngine:
         form = {"moments": 0, "beam": 1, "entry": 2}.get(form, form)
         self._chk(self.lib.icm_set_energy_form(self.h, int(form)))
 
-    def set_solve_lanes(self, mode):
-        """-1 automatic, 0 one lane per pose, 1 one quad per pose (latency form)."""
-        self._chk(self.lib.icm_set_solve_lanes(self.h, int(mode)))
-
     def snapshot_state(self):
         """Keep a device-side copy of the current sweep state (poses, map, search structures)."""
         self._chk(self.lib.icm_snapshot_state(self.h))

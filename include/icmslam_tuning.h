@@ -41,9 +41,8 @@ int icm_get_runs(icm_handle *h, int64_t *offsets, double *centre_xy, double *sum
  * stop event for the rest of its life.  icm_get_wait_giveups: how many sweeps that happened to (0 in a normal run; a
  * profile taken under serialisation shows the event path from the second sweep on). */
 int icm_get_wait_giveups(const icm_handle *h, int64_t *sweeps);
-/* Environment knobs read once at icm_create (A/B measurements; results identical): ICM_L3_EVENT=1 starts the side stream
- * by k_lm_l3's stop event from the first sweep (what a give-up switches to); ICM_SOLVE_PPW=32|64 fixes the poses per wave
- * of the one-launch solve (default: 64, 32 for short colours). */
+/* Environment knob read once at icm_create (A/B measurements; results identical): ICM_L3_EVENT=1 starts the side stream
+ * by k_lm_l3's stop event from the first sweep (what a give-up switches to). */
 
 /* Keep the per-beam outputs of a sweep (label and running-mean target of every kept beam)
  * for icm_get_association; off by default (they cost 28 B of HBM traffic per kept beam). */
@@ -61,13 +60,7 @@ int icm_get_solve_diag(icm_handle *h, double *out);
  * Forms 1 and 2 exist to cross-check form 0. */
 int icm_set_energy_form(icm_handle *h, int form);
 
-/* Lanes per pose in the red-black solves: 0 / -1 (default) = one lane per pose (throughput form, both colours in one
- * launch), 1 = one DPP quad per pose evaluating the four candidate points of a Nelder-Mead iteration at once (latency
- * form, kept as a cross-check: one launch per colour; measured slower at every size since the folded energy).
- * Bit-identical results. */
-int icm_set_solve_lanes(icm_handle *h, int mode);
-
-/* Red-black sweeps in throughput form: 1 (default) = both colours in ONE launch, every
+/* Red-black sweeps in moment form: 1 (default) = both colours in ONE launch, every
  * even wave starting as soon as the two odd waves holding its poses' neighbours are done
  * (k_solve_m_fused); 0 = one launch per colour.  Bit-identical results. */
 int icm_set_colour_fusion(icm_handle *h, int on);

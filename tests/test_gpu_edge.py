@@ -484,60 +484,34 @@ def test_handle_reuse_with_longer_sequence():
     assert np.array_equal(outs[1][0], x2) and np.array_equal(outs[1][1], mo2[:, :K2])
 
 
-def test_quad_latency_solver_is_bit_identical():
-    """The four-lanes-per-pose (speculative) Nelder-Mead against the one-lane form: same poses,
-    same iteration / evaluation counts, on the real dataset (red-black) and a synthetic one."""
-    from ICM_SLAM_tools import ConfigICM
+def test_sequential_chain_folded_and_complete_energy_are_bit_identical():
+    """The reference's own order (one dependent chain, scripts/ICM_ROS.py:141-158) walked by one lane with the folded
+    energy in the loop (automatic) and with the complete energy there (fold mode 0): same poses, same iteration /
+    evaluation counts of every pose, on the real dataset."""
     from icmslam_hip import SweepEngine
-    from icmslam_hip.synthetic import make_workload
     zz, odo, u = dataset()
     init = gold("init_pass.npz")
     eng = SweepEngine(Cfg())
     eng.upload(zz, odo, u)
     eng.set_debug(True)
-    res = {}
-    for mode in (0, 1):
-        eng.set_solve_lanes(mode)
-        eng.set_state(init["map_init"], init["x_init"], odo[:, 0], 11)
-        for _ in range(2):
-            eng.sweep_device("redblack")
-        res[mode] = (eng.get_state(), eng.solve_diag().copy())
+    eng.set_state(init["map_init"], init["x_init"], odo[:, 0], 11)
+    for _ in range(2):
+        eng.sweep_device("redblack")
+    assert eng.solve_diag()[:, 2].max() > 60             # (the red-black solve reports f, nit, nfev of every pose too)
     eng.close()
-    for a, b in zip(res[0][0], res[1][0]):
-        assert np.array_equal(a, b)
-    assert np.array_equal(res[0][1], res[1][1])          # f, nit, nfev of every pose
-    assert res[0][1][:, 2].max() > 60
-    # the reference's own order (one dependent chain, scripts/ICM_ROS.py:141-158) walked by one lane / one DPP quad, with the
-    # folded energy in the loop (automatic) and with the complete energy there (fold mode 0): poses, f, nit, nfev identical
     eng = SweepEngine(Cfg())
     eng.upload(zz, odo, u)
     eng.set_debug(True)
     seq = {}
     for fold in (-1, 0):
-        for mode in (0, 1):
-            eng.set_fold_mode(fold)
-            eng.set_solve_lanes(mode)
-            eng.set_state(init["map_init"], init["x_init"], odo[:, 0], 11)
-            eng.sweep_device("sequential")
-            seq[(fold, mode)] = (eng.get_state(), eng.solve_diag().copy())
+        eng.set_fold_mode(fold)
+        eng.set_state(init["map_init"], init["x_init"], odo[:, 0], 11)
+        eng.sweep_device("sequential")
+        seq[fold] = (eng.get_state(), eng.solve_diag().copy())
     eng.close()
-    for key in ((-1, 1), (0, 0), (0, 1)):
-        for a, b in zip(seq[(-1, 0)][0], seq[key][0]):
-            assert np.array_equal(a, b), key
-        assert np.array_equal(seq[(-1, 0)][1][:, 1:], seq[key][1][:, 1:]), key     # nit, nfev of every pose
-    wl = make_workload(1900, 100, 180)
-    e2 = SweepEngine(ConfigICM(D=wl.config))
-    e2.upload(wl.scans, wl.odometry, wl.u, pose_major=True)
-    out = []
-    for mode in (0, 1):
-        e2.set_solve_lanes(mode)
-        e2.set_state(wl.map_init, wl.x_init, wl.x0)
-        for _ in range(3):
-            e2.sweep_device("redblack")
-        out.append(e2.get_state())
-    e2.close()
-    for a, b in zip(out[0], out[1]):
+    for a, b in zip(seq[-1][0], seq[0][0]):
         assert np.array_equal(a, b)
+    assert np.array_equal(seq[-1][1][:, 1:], seq[0][1][:, 1:])     # nit, nfev of every pose
 
 
 def test_fused_two_colour_launch_is_bit_identical():
@@ -547,7 +521,7 @@ def test_fused_two_colour_launch_is_bit_identical():
     from ICM_SLAM_tools import ConfigICM
     from icmslam_hip import SweepEngine
     from icmslam_hip.synthetic import make_workload
-    wl = make_workload(40_000, 4_000, 360)     # > 32768 poses: the throughput form of the solves
+    wl = make_workload(40_000, 4_000, 360)     # long: 64 poses per wave in the one-launch solve
     cfg = ConfigICM(D=wl.config)
     eng = SweepEngine(cfg)
     eng.upload(wl.scans, wl.odometry, wl.u, pose_major=True)
@@ -565,7 +539,7 @@ def test_fused_two_colour_launch_is_bit_identical():
     eng.close()
     assert np.array_equal(out[False][0], out[True][0]) and np.array_equal(out[False][1], out[True][1])
     assert out[False][3] == out[True][3] and np.array_equal(out[False][2], out[True][2])
-    # short sequences use the latency form (one quad per pose): the same fusion, 16 poses per wave
+    # a short sequence: the same fusion, 32 poses per wave
     zz, odo, u = dataset()
     init = gold("init_pass.npz")
     e2 = SweepEngine(Cfg())
@@ -639,7 +613,6 @@ def _s1_state_after(sweeps, setup):
     wl = make_workload(*WORKLOADS["S1"])
     eng = SweepEngine(ConfigICM(D=wl.config))
     eng.upload(wl.scans, wl.odometry, wl.u, pose_major=True)
-    eng.set_solve_lanes(0)          # throughput form (S1 alone would pick the latency form)
     setup(eng)
     eng.set_state(wl.map_init, wl.x_init, wl.x0)
     for _ in range(sweeps):
@@ -654,15 +627,15 @@ def test_fused_solve_defers_instead_of_depending_on_dispatch_order():
     wave that does not see its neighbours' flags within the poll budget leaves its poses alone and
     the wave that finishes the launch last solves them (inside the same launch: nothing is queued
     behind a solve launch).  With a budget of 0 polls nearly every even wave takes that road -- the
-    result is bit-identical to the default, to one launch per colour and to the quad form (which
-    always runs one launch per colour), and the default run defers nothing."""
+    result is bit-identical to the default and to one launch per colour (with a budget of 0 polls
+    too: nothing to defer there), and the default run defers nothing."""
     (ref, nd_ref) = _s1_state_after(3, lambda e: None)
     (two, _) = _s1_state_after(3, lambda e: e.set_colour_fusion(False))
     (zero, nd_zero) = _s1_state_after(3, lambda e: e.set_fused_spin_limit(0))
-    (quad0, nd_q) = _s1_state_after(3, lambda e: (e.set_solve_lanes(1), e.set_fused_spin_limit(0)))
-    print("even waves deferred: default %d, 0 polls %d (lane form) / %d (quad form: one launch per colour)" % (nd_ref, nd_zero, nd_q))
-    assert nd_ref == 0 and nd_zero > 0 and nd_q == 0
-    for other in (two, zero, quad0):
+    (two0, nd_two0) = _s1_state_after(3, lambda e: (e.set_colour_fusion(False), e.set_fused_spin_limit(0)))
+    print("even waves deferred: default %d, 0 polls %d (one launch) / %d (one launch per colour)" % (nd_ref, nd_zero, nd_two0))
+    assert nd_ref == 0 and nd_zero > 0 and nd_two0 == 0
+    for other in (two, zero, two0):
         for a, b in zip(ref, other):
             assert np.array_equal(a, b)
 
@@ -707,7 +680,6 @@ def test_three_engines_on_concurrent_streams_equal_their_solo_runs():
     for wl in wls:
         e = SweepEngine(ConfigICM(D=wl.config), 0)
         e.upload(wl.scans, wl.odometry, wl.u, pose_major=True)
-        e.set_solve_lanes(0)
         e.set_state(wl.map_init, wl.x_init, wl.x0)
         e.snapshot_state()
         engs.append(e)
@@ -946,12 +918,12 @@ def test_fixup_launches_take_poses_outside_the_folded_range():
         assert d.max() <= 1e-9
 
 
-def test_fixup_launches_with_deferred_waves_and_quad_form():
+def test_fixup_launches_with_deferred_waves_and_per_colour_launches():
     """Both rare roads of the one-launch solve at once: poses outside the folded form's range (solved a second time by
     their wave) and even waves that deferred (solved by the launch's last wave).  With the poll budget at 0 EVERY even
     wave whose odd neighbours are not done at its first look defers; with kicked headings some poses leave the folded
-    range on top of that -- lane form, and the quad form (one launch per colour) beside it, all against the
-    complete-energy kernel with the default poll budget: bit-identical."""
+    range on top of that -- and one launch per colour beside it, all against the complete-energy one-launch kernel with
+    the default poll budget: bit-identical."""
     from ICM_SLAM_tools import ConfigICM
     from icmslam_hip import SweepEngine
     from icmslam_hip.synthetic import make_workload
@@ -961,11 +933,11 @@ def test_fixup_launches_with_deferred_waves_and_quad_form():
     x0[2, 45:wl.T - 2:50] += 0.4
     x0[2, 70:wl.T - 2:100] -= 0.4
     outs = []
-    for fold, lanes, spin in ((0, 0, None), (1, 0, 0), (1, 1, 0), (1, 1, None), (0, 1, 0)):
+    for fold, fuse, spin in ((0, True, None), (1, True, 0), (1, False, 0), (0, False, None)):
         eng = SweepEngine(cfg)
         eng.upload(wl.scans, wl.odometry, wl.u, pose_major=True)
         eng.set_fold_mode(fold)
-        eng.set_solve_lanes(lanes)
+        eng.set_colour_fusion(fuse)
         if spin is not None:
             eng.set_fused_spin_limit(spin)
         eng.set_state(wl.map_init, x0, wl.x0)
