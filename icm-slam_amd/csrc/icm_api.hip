@@ -1079,6 +1079,30 @@ static bool optimistic_applies(const icm_handle* h) {
     return h->form == 0 && h->entry_path != 0 && h->hier_ok && !h->debug && !h->per_beam && !h->brute && h->gpu_filtrar && !h->timing;
 }
 
+// Buffers of phase A's association of `nloc` poses: the main shard's, or the ghost pose's (its gh_* buffers, nloc = 1).
+struct AssocIO {
+    const int* boff; const double2* bxy; const int* roff; const double2* r_s; const uint2* r_m; const double* rot; const int* plan; int nloc, t_begin;
+    int *label, *bloc, *st_label; unsigned short* st_k; double *st_sx, *st_sy; int *nent, *isnew, *flags; int nnz; int* st_off; int sparse0; unsigned long long* run_counts;
+};
+enum AssocForm { kAssocBrute, kAssocRuns, kAssocBeams };   // beam by beam with k_associate_brute's labels / by runs / beam by beam
+// The form's instantiation for `dbg` (label[] and the beam -> entry map bloc[] too) and `hs` hash slots, on stream `s`.
+static void launch_assoc(icm_handle* h, const AssocIO& a, hipStream_t s, AssocForm form, bool dbg, int hs) {
+    const GridView gv{h->gpar.p, h->g_cell.p, h->g_lm.p, h->g_nb.p};
+    if (form == kAssocRuns) {
+        static const decltype(&k_assoc_runs<false, 128>) fns[2][2] = {{k_assoc_runs<false, 128>, k_assoc_runs<false, 256>}, {k_assoc_runs<true, 128>, k_assoc_runs<true, 256>}};
+        const float thr_margin = (float)(1e-4 * h->cfg.dist_thr), thr_m = (float)h->cfg.dist_thr - thr_margin;
+        fns[dbg][hs != 128]<<<nblocks_waves(a.nloc), kBlock, 0, s>>>(h->x, a.roff, a.r_s, a.rot, h->gpar.p, a.plan, a.nloc, a.t_begin, h->x0.p, a.r_m,
+            a.boff, a.bxy, gv, h->cfg.dist_thr, h->thr2, thr_m, thr_margin, a.label, a.bloc, a.st_label, a.st_k, a.st_sx, a.st_sy, a.nent, a.isnew, a.flags,
+            a.nnz, a.st_off, 0, a.sparse0, a.run_counts);
+        return;
+    }
+    static const decltype(&k_assoc_group<false, false, 128>) fns[2][2][2] = {
+        {{k_assoc_group<false, false, 128>, k_assoc_group<false, false, 256>}, {k_assoc_group<false, true, 128>, k_assoc_group<false, true, 256>}},
+        {{k_assoc_group<true, false, 128>, k_assoc_group<true, false, 256>}, {k_assoc_group<true, true, 128>, k_assoc_group<true, true, 256>}}};
+    fns[form == kAssocBrute][dbg][hs != 128]<<<nblocks_waves(a.nloc), kBlock, 0, s>>>(h->x, a.boff, a.bxy, a.rot, h->gpar.p, a.plan, a.nloc, a.t_begin,
+        h->x0.p, gv, h->cfg.dist_thr, h->thr2, a.label, a.bloc, a.st_label, a.st_k, a.st_sx, a.st_sy, a.nent, a.isnew, a.flags, a.nnz, a.st_off, 0, a.sparse0);
+}
+
 // Phase A + local statistics.
 int icm_sweep_local(icm_handle* h) {
     if (!h) return ICM_ERR_ARG;
@@ -1107,19 +1131,11 @@ int icm_sweep_local(icm_handle* h) {
     h->fl = h->flags.p + 16 * h->fl_parity;
     if (!h->fl_next_clean) HIPCHK(h, hipMemsetAsync(h->fl, 0, 16 * sizeof(int), h->stream));   // (else the last sweep's k_lm_l3 cleared it)
     h->fl_next_clean = false;
-    GridView gv{h->gpar.p, h->g_cell.p, h->g_lm.p, h->g_nb.p};
     const bool dbg = h->debug || h->per_beam;
     h->assoc_kept = dbg;
-#define ASSOC_ARGS h->x, h->boff.p, h->bxy.p, h->rot.p, h->gpar.p, h->ent_off.p, nloc, (int)h->t_begin, h->x0.p, gv, h->cfg.dist_thr, h->thr2, h->label.p, \
-        h->bloc.p, h->st_label.p, h->st_k.p, h->st_sx.p, h->st_sy.p, h->nent.p, h->isnew.p, h->fl, (int)h->nnz, h->st_off.p, 0, (int)h->stl.sparse0
-#define ASSOC_GROUP(PRE, DBG, HS) TIMED(h, KID_ASSOC_GROUP, (k_assoc_group<PRE, DBG, HS><<<nblocks_waves(nloc), kBlock, 0, h->stream>>>(ASSOC_ARGS)))
-#define ASSOC_GROUP_HS(PRE, DBG) do { if (h->hash_slots == 128) ASSOC_GROUP(PRE, DBG, 128); else ASSOC_GROUP(PRE, DBG, 256); } while (0)
-    const float thr_margin = (float)(1e-4 * h->cfg.dist_thr), thr_m = (float)h->cfg.dist_thr - thr_margin;
-#define ASSOC_RUNS(DBG, HS) TIMED(h, KID_ASSOC_RUNS, (k_assoc_runs<DBG, HS><<<nblocks_waves(nloc), kBlock, 0, h->stream>>>( \
-        h->x, h->roff.p, h->r_s.p, h->rot.p, h->gpar.p, h->ent_off.p, nloc, (int)h->t_begin, h->x0.p, h->r_m.p, h->boff.p, h->bxy.p, gv, \
-        h->cfg.dist_thr, h->thr2, thr_m, thr_margin, h->label.p, h->bloc.p, h->st_label.p, h->st_k.p, h->st_sx.p, h->st_sy.p, h->nent.p, h->isnew.p, h->fl, \
-        (int)h->nnz, h->st_off.p, 0, (int)h->stl.sparse0, h->run_counts.p)))
-#define ASSOC_RUNS_HS(DBG) do { if (h->hash_slots == 128) ASSOC_RUNS(DBG, 128); else ASSOC_RUNS(DBG, 256); } while (0)
+    const AssocIO assoc{h->boff.p, h->bxy.p, h->roff.p, h->r_s.p, h->r_m.p, h->rot.p, h->ent_off.p, nloc, (int)h->t_begin, h->label.p, h->bloc.p,
+        h->st_label.p, h->st_k.p, h->st_sx.p, h->st_sy.p, h->nent.p, h->isnew.p, h->fl, (int)h->nnz, h->st_off.p, (int)h->stl.sparse0, h->run_counts.p};
+    const AssocForm form = h->brute ? kAssocBrute : h->assoc_form == 1 ? kAssocRuns : kAssocBeams;
     if (!h->rot_valid) {   // (the poses came from the host, a snapshot or a solve form that does not keep the table)
         TIMED(h, KID_POSE_ROT, (k_pose_rot<<<nblocks_threads(nloc), kBlock, 0, h->stream>>>(h->x, h->x0.p, (int)h->t_begin, nloc, h->rot.p, h->pose_cs.p)));
         h->rot_valid = true;
@@ -1141,13 +1157,7 @@ int icm_sweep_local(icm_handle* h) {
     double* const ms = h->ms.p;
     const size_t msn = (size_t)h->nsuper * (size_t)L;
     for (;;) {
-        if (h->brute) {
-            if (dbg) ASSOC_GROUP_HS(true, true); else ASSOC_GROUP_HS(true, false);
-        } else if (h->assoc_form == 1) {   // by runs: the bounding-circle test, beam by beam where it does not settle
-            if (dbg) ASSOC_RUNS_HS(true); else ASSOC_RUNS_HS(false);
-        } else {
-            if (dbg) ASSOC_GROUP_HS(false, true); else ASSOC_GROUP_HS(false, false);
-        }
+        TIMED(h, form == kAssocRuns ? KID_ASSOC_RUNS : KID_ASSOC_GROUP, launch_assoc(h, assoc, h->stream, form, dbg, h->hash_slots));
         h->map_ev_in_local = false;
         if (!run_scan && ++h->scan_epoch == 0u) ++h->scan_epoch;   // (tag 0 = never written)
         if (run_scan) {
@@ -1214,11 +1224,6 @@ int icm_sweep_local(icm_handle* h) {
         }
         break;
     }
-#undef ASSOC_RUNS_HS
-#undef ASSOC_RUNS
-#undef ASSOC_GROUP_HS
-#undef ASSOC_GROUP
-#undef ASSOC_ARGS
     if (h->optimistic && hier) {
         h->path_used = 1;
         if (h->world > 1)
@@ -1275,15 +1280,9 @@ static int launch_ghost(icm_handle* h) {
     }
     int* gm = h->gh_misc.p;   // [0] nent [1] isnew [2] st_off [3..4] reservation plan (zeros) [8..23] the ghost launch's flags
     HIPCHK(h, hipMemsetAsync(gm + 8, 0, 16 * sizeof(int), gs));
-    if (h->assoc_form == 1) {   // (the form its owner's rank uses: the ghost's entries carry the owner's sums bit for bit)
-        const float thr_margin = (float)(1e-4 * h->cfg.dist_thr), thr_m = (float)h->cfg.dist_thr - thr_margin;
-        k_assoc_runs<false, 256><<<1, kBlock, 0, gs>>>(h->x, h->gh_roff.p, h->gh_rs.p, h->gh_rot.p, h->gpar.p, gm + 3, 1, (int)h->t_begin - 1, h->x0.p,
-            h->gh_rm.p, h->gh_boff.p, h->gh_bxy.p, GridView{h->gpar.p, h->g_cell.p, h->g_lm.p, h->g_nb.p}, h->cfg.dist_thr, h->thr2, thr_m, thr_margin,
-            h->gh_label.p, h->gh_bloc.p, h->gh_st_label.p, h->gh_st_k.p, h->gh_sx.p, h->gh_sy.p, gm, gm + 1, gm + 8, h->ghost_n, gm + 2, 0, kWave, nullptr);
-    } else
-    k_assoc_group<false, false, 256><<<1, kBlock, 0, gs>>>(h->x, h->gh_boff.p, h->gh_bxy.p, h->gh_rot.p, h->gpar.p, gm + 3, 1, (int)h->t_begin - 1, h->x0.p,
-        GridView{h->gpar.p, h->g_cell.p, h->g_lm.p, h->g_nb.p}, h->cfg.dist_thr, h->thr2, h->gh_label.p, h->gh_bloc.p, h->gh_st_label.p,
-        h->gh_st_k.p, h->gh_sx.p, h->gh_sy.p, gm, gm + 1, gm + 8, h->ghost_n, gm + 2, 0, kWave);
+    const AssocIO assoc{h->gh_boff.p, h->gh_bxy.p, h->gh_roff.p, h->gh_rs.p, h->gh_rm.p, h->gh_rot.p, gm + 3, 1, (int)h->t_begin - 1, h->gh_label.p,
+        h->gh_bloc.p, h->gh_st_label.p, h->gh_st_k.p, h->gh_sx.p, h->gh_sy.p, gm, gm + 1, gm + 8, h->ghost_n, gm + 2, kWave, nullptr};
+    launch_assoc(h, assoc, gs, h->assoc_form == 1 ? kAssocRuns : kAssocBeams, false, 256);   // (the form its owner's rank uses: the ghost's entries carry the owner's sums bit for bit)
     k_ghost_moments<<<1, kWave, 0, gs>>>(h->x, (int)h->t_begin - 1, gm, gm + 2, h->gh_st_label.p, h->gh_st_k.p, h->gh_sx.p, h->gh_sy.p,
         h->gh_s2.p, h->gh_rot.p, h->off_sx.p, h->off_sy.p, h->off_n.p,
         h->stats_all + (size_t)(h->rank - 1) * (size_t)icm_stats_stride(h), L, h->lact0, h->gh_m.p, gm + 8, h->fl);

@@ -654,6 +654,37 @@ __global__ __launch_bounds__(kBlock) void k_neigh_table(GridView g, NeighRec* __
     out[c].id3 = id[3];
 }
 
+// The literal cdist / argmin (first index on ties) / gate of the reference for the world point (wx, wy) against the
+// first K landmarks, the table tiled through LDS (sx, sy: kBruteTile doubles each) by the whole workgroup.  Every thread
+// of the workgroup calls it the same number of times (two barriers per tile); `on` says whether its point counts.
+// Returns the landmark's index, or -1 when gated out.
+constexpr int kBruteTile = 1024;
+__device__ __forceinline__ int nearest_landmark(double* sx, double* sy, const double* mapx,
+                                                const double* mapy, int K, double thr, bool on, double wx,
+                                                double wy) {
+    double best = __builtin_huge_val();
+    int bid = -1;
+    for (int k0 = 0; k0 < K; k0 += kBruteTile) {
+        __syncthreads();
+        for (int k = threadIdx.x; k < kBruteTile && k0 + k < K; k += kBlock) {
+            sx[k] = mapx[k0 + k];
+            sy[k] = mapy[k0 + k];
+        }
+        __syncthreads();
+        const int kn = min(kBruteTile, K - k0);
+        if (on)
+            for (int k = 0; k < kn; ++k) {
+                const double dx = sx[k] - wx, dy = sy[k] - wy;
+                const double d = sqrt(dx * dx + dy * dy);
+                if (d < best) {
+                    best = d;
+                    bid = k0 + k;
+                }
+            }
+    }
+    return (bid >= 0 && !(best > thr)) ? bid : -1;
+}
+
 // Brute-force form of the same association (all K landmarks, table tiled through LDS): the
 // literal cdist/argmin of the reference.  Writes labels only; used to cross-check the grid
 // search on the GPU (k_assoc_group<PRELABEL> then consumes the labels).
@@ -662,8 +693,7 @@ __global__ __launch_bounds__(kBlock) void k_associate_brute(const double* __rest
                                                             const double* __restrict__ bx, const double* __restrict__ by,
                                                             const double* __restrict__ mapx, const double* __restrict__ mapy,
                                                             int K, double thr, int* __restrict__ label) {
-    constexpr int TILE = 1024;
-    __shared__ double sx[TILE], sy[TILE];
+    __shared__ double sx[kBruteTile], sy[kBruteTile];
     __shared__ int s_maxit;
     const int lane = lane_id();
     const int tl = blockIdx.x * kWavesPerBlock + wave_in_block();
@@ -691,27 +721,8 @@ __global__ __launch_bounds__(kBlock) void k_associate_brute(const double* __rest
             wx = (bx[j] * ct - by[j] * st) + px;
             wy = (bx[j] * st + by[j] * ct) + py;
         }
-        double best = __builtin_huge_val();
-        int bid = -1;
-        for (int k0 = 0; k0 < K; k0 += TILE) {
-            __syncthreads();
-            for (int k = threadIdx.x; k < TILE && k0 + k < K; k += kBlock) {
-                sx[k] = mapx[k0 + k];
-                sy[k] = mapy[k0 + k];
-            }
-            __syncthreads();
-            const int kn = min(TILE, K - k0);
-            if (on)
-                for (int k = 0; k < kn; ++k) {
-                    const double dx = sx[k] - wx, dy = sy[k] - wy;
-                    const double d = sqrt(dx * dx + dy * dy);
-                    if (d < best) {
-                        best = d;
-                        bid = k0 + k;
-                    }
-                }
-        }
-        if (on) label[j] = (bid >= 0 && !(best > thr)) ? bid : -1;
+        const int lab = nearest_landmark(sx, sy, mapx, mapy, K, thr, on, wx, wy);
+        if (on) label[j] = lab;
     }
 }
 
@@ -722,8 +733,7 @@ __global__ __launch_bounds__(kBlock) void k_associate_brute(const double* __rest
 __global__ __launch_bounds__(kBlock) void k_scan_labels(const double* __restrict__ obs, int n,
                                                         const double* __restrict__ mapx, const double* __restrict__ mapy,
                                                         int K, double thr, int* __restrict__ label) {
-    constexpr int TILE = 1024;
-    __shared__ double sx[TILE], sy[TILE];
+    __shared__ double sx[kBruteTile], sy[kBruteTile];
     const int j = blockIdx.x * kBlock + threadIdx.x;
     const bool on = j < n;
     double wx = 0.0, wy = 0.0;
@@ -731,27 +741,8 @@ __global__ __launch_bounds__(kBlock) void k_scan_labels(const double* __restrict
         wx = obs[2 * (size_t)j];
         wy = obs[2 * (size_t)j + 1];
     }
-    double best = __builtin_huge_val();
-    int bid = -1;
-    for (int k0 = 0; k0 < K; k0 += TILE) {
-        __syncthreads();
-        for (int k = threadIdx.x; k < TILE && k0 + k < K; k += kBlock) {
-            sx[k] = mapx[k0 + k];
-            sy[k] = mapy[k0 + k];
-        }
-        __syncthreads();
-        const int kn = min(TILE, K - k0);
-        if (on)
-            for (int k = 0; k < kn; ++k) {
-                const double dx = sx[k] - wx, dy = sy[k] - wy;
-                const double d = sqrt(dx * dx + dy * dy);
-                if (d < best) {
-                    best = d;
-                    bid = k0 + k;
-                }
-            }
-    }
-    if (on) label[j] = (bid >= 0 && !(best > thr)) ? bid : -1;
+    const int lab = nearest_landmark(sx, sy, mapx, mapy, K, thr, on, wx, wy);
+    if (on) label[j] = lab;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -831,6 +822,106 @@ struct PoseTable {
     int owner[HS];
 };
 
+// The operations of both phase-A kernels on their pose's table (one wave per table).
+template <int HS>
+__device__ __forceinline__ void table_clear(PoseTable<HS>& T) {
+    for (int s = lane_id(); s < HS; s += kWave) {
+        T.key[s] = kEmpty;
+        T.cnt[s] = 0;
+        T.sx[s] = 0.0;
+        T.sy[s] = 0.0;
+    }
+}
+
+template <int HS>
+__device__ __forceinline__ int table_home(int lab) {
+    return (int)(((unsigned)lab * 2654435761u) >> (HS == 128 ? 25 : 24));
+}
+
+// One probe: claims `slot` for `lab` if it is free; returns the label that held it before (kEmpty: claimed).
+template <int HS>
+__device__ __forceinline__ int table_cas(PoseTable<HS>& T, int slot, int lab) {
+    return atomicCAS(&T.key[slot], kEmpty, lab);
+}
+
+// Continues the linear probe for `lab` from `slot`, whose table_cas returned `held` (issued by the caller, which may
+// cover its round trip with other work).  Returns whether the label's slot was found; `slot` is then that slot and
+// `inserted` whether this lane claimed it.  Bounded: the table is checked against its 3/4 budget only between chunks,
+// and one chunk can bring up to 64 new labels -- a full table must end the probe, not spin.
+template <int HS>
+__device__ __forceinline__ bool table_probe(PoseTable<HS>& T, int lab, int& slot, int held, bool& inserted) {
+    for (int probes = 0; probes < HS; ++probes) {
+        if (held == kEmpty || held == lab) {
+            inserted = held == kEmpty;
+            return true;
+        }
+        slot = (slot + 1) & (HS - 1);
+        held = table_cas(T, slot, lab);
+    }
+    return false;
+}
+
+// Adds a partial entry (k beams, sum of their body points) to a slot by LDS atomics (ds_add_u32 / ds_add_f64, no return
+// value): no read-modify-write round trip, and two partials of one label (a landmark seen left and right of an occluder)
+// need no arbitration -- the LDS serialises the two additions itself, in one fixed order.
+template <int HS>
+__device__ __forceinline__ void table_add(PoseTable<HS>& T, int slot, int k, double sbx, double sby) {
+    atomicAdd(&T.cnt[slot], k);
+    lds_add_f64(&T.sx[slot], sbx);
+    lds_add_f64(&T.sy[slot], sby);
+}
+
+// Compacts the used slots into the pose's place, slot order: its reserved one [plan0, plan1) if the entries fit, else the
+// front of its own beam range (first kept beam j0) in the sparse area; then the pose's header words.  DEBUG: T.owner[s] =
+// the entry index of slot s (table_remap).
+template <bool DEBUG, int HS>
+__device__ __forceinline__ void table_stage(PoseTable<HS>& T, int tl, int j0, int nent, bool overflow, int plan0,
+                                            int plan1, int nnz_total, int pose0, int sparse0, int* st_label,
+                                            unsigned short* st_k, double* st_sbx,
+                                            double* st_sby, int* nent_out,
+                                            int* isnew_out, int* flags, int* st_off) {
+    const int lane = lane_id();
+    const int room = (plan1 - plan0) + kStageSlack;
+    const bool fits = plan0 >= 0 && plan1 >= plan0 && plan1 <= nnz_total && nent <= room;   // (a stale plan is still a plan; a wild one is not)
+    const int sbase = fits ? plan0 + kStageSlack * (pose0 + tl) : sparse0 + j0;
+    int written = 0;
+    bool isnew = false;
+    for (int s0 = 0; s0 < HS; s0 += kWave) {
+        const int s = s0 + lane;
+        const int k = T.key[s];
+        const bool occ = k != kEmpty;
+        const unsigned long long mask = __ballot(occ);
+        if (occ) {
+            const unsigned q = (unsigned)(written + prefix_count(mask, lane));   // (scalar bases + 32-bit offsets, like the beam loads)
+            *reinterpret_cast<int*>(reinterpret_cast<char*>(st_label + sbase) + (q << 2)) = k;
+            *reinterpret_cast<unsigned short*>(reinterpret_cast<char*>(st_k + sbase) + (q << 1)) = (unsigned short)T.cnt[s];   // (beams of one scan: <= B <= kMaxBeams)
+            *reinterpret_cast<double*>(reinterpret_cast<char*>(st_sbx + sbase) + (q << 3)) = T.sx[s];
+            *reinterpret_cast<double*>(reinterpret_cast<char*>(st_sby + sbase) + (q << 3)) = T.sy[s];
+            isnew |= k == -1;
+            if (DEBUG) T.owner[s] = q;
+        }
+        written += __popcll(mask);
+    }
+    const unsigned long long anynew = __ballot(isnew);
+    if (lane == 0) {
+        nent_out[tl] = written;
+        st_off[tl] = sbase;
+        isnew_out[tl] = anynew != 0ull;
+        // poses outside their reserved place: the host refreshes the plan when many (not counted while there is no plan
+        // at all -- the first sweep of a sequence: 100 000 atomics on one word)
+        if (!fits && plan1 > 0) atomicAdd(&flags[3], 1);
+        if (overflow) flags[0] = 1;
+    }
+}
+
+// DEBUG: the beam -> slot map of the pose's beams [j0, j1) in bloc becomes beam -> entry index within the pose.
+template <int HS>
+__device__ __forceinline__ void table_remap(const PoseTable<HS>& T, int j0, int j1, int* bloc) {
+    __builtin_amdgcn_wave_barrier();
+    __threadfence_block();
+    for (int j = j0 + lane_id(); j < j1; j += kWave) bloc[j] = T.owner[bloc[j]];
+}
+
 // One wave per pose, four poses per 256-thread workgroup.  (Measured and dropped, DESIGN.md appendix: several consecutive
 // poses per wave with the next pose's header and first beams in flight -- 0.192 / 0.202 / 0.217 ms at 1 / 2 / 4 poses per
 // wave; persistent waves striding over the poses -- +19 % .. +51 %; one-wave workgroups -- no difference.)
@@ -857,8 +948,7 @@ void k_assoc_group(const double* __restrict__ x, const int* __restrict__ boff, c
                                                         int* __restrict__ isnew_out, int* __restrict__ flags,
                                                         int nnz_total = 0, int* __restrict__ st_off = nullptr,
                                                         int pose0 = 0, int sparse0 = 0) {
-    constexpr int kHash = HS, kGroupCap = HS * 3 / 4;
-    constexpr int kHashShift = HS == 128 ? 25 : 24;
+    constexpr int kGroupCap = HS * 3 / 4;
     __shared__ PoseTable<HS> tables[kWavesPerBlock];
     const int lane = lane_id();
     const int tl = __builtin_amdgcn_readfirstlane(blockIdx.x * kWavesPerBlock + wave_in_block());
@@ -898,12 +988,7 @@ void k_assoc_group(const double* __restrict__ x, const int* __restrict__ boff, c
     }
     const double2* __restrict__ bxyp = bxy + j0;
     const unsigned nbeam = (unsigned)(j1 - j0);
-    for (int s = lane; s < kHash; s += kWave) {
-        T.key[s] = kEmpty;
-        T.cnt[s] = 0;
-        T.sx[s] = 0.0;
-        T.sy[s] = 0.0;
-    }
+    table_clear(T);
     int nent = 0;
     bool overflow = false;
     __builtin_amdgcn_wave_barrier();
@@ -953,9 +1038,9 @@ void k_assoc_group(const double* __restrict__ x, const int* __restrict__ boff, c
         // Run tails claim / find the slot of their label in the pose's LDS table.  The compare-and-swap on the label's
         // home slot goes out NOW, in front of the segmented scan (vector / DPP work only), whose instructions cover its
         // round trip; it either claims the free slot or reports who holds it.
-        int slot = (int)(((unsigned)lab * 2654435761u) >> kHashShift);
+        int slot = table_home<HS>(lab);
         int held = kEmpty;
-        if (tail) held = atomicCAS(&T.key[slot], kEmpty, lab);
+        if (tail) held = table_cas(T, slot, lab);
         // Segmented inclusive scan of (bx, by) over the runs, over the distance to the run head: at step d a lane at least
         // d beams into its run adds the partial of lane - d; the partials move through DPP row shifts / row broadcasts.
         // (Round 3 measured the same scan with the partials travelling through LDS -- one 16-byte write and read per lane
@@ -973,30 +1058,11 @@ void k_assoc_group(const double* __restrict__ x, const int* __restrict__ boff, c
         // ... the slot search goes on only where the home slot holds another label (linear probing; a probe IS the
         // compare-and-swap: one LDS round trip per step instead of a read and then a swap)
         bool inserted = false, found = false;
-        if (tail) {
-            // bounded: the table is checked against its 3/4 budget only between chunks, and one
-            // chunk can bring up to 64 new labels -- a full table must end the probe, not spin
-            for (int probes = 0; probes < kHash; ++probes) {
-                if (held == kEmpty || held == lab) {
-                    inserted = held == kEmpty;
-                    found = true;
-                    break;
-                }
-                slot = (slot + 1) & (kHash - 1);
-                held = atomicCAS(&T.key[slot], kEmpty, lab);
-            }
-        }
+        if (tail) found = table_probe(T, lab, slot, held, inserted);
         if (__ballot(tail && !found) != 0ull) overflow = true;   // more distinct landmarks than slots
         tail = tail && found;
         nent += __popcll(__ballot(inserted));
-        // The run's totals are ADDED to the slot by LDS atomics (ds_add_u32 / ds_add_f64, no return value): no
-        // read-modify-write round trip, and two runs of one label inside a batch (a landmark seen left and right of an
-        // occluder) need no arbitration -- the LDS serialises the two additions itself, in one fixed order.
-        if (tail) {
-            atomicAdd(&T.cnt[slot], c);
-            lds_add_f64(&T.sx[slot], ax);
-            lds_add_f64(&T.sy[slot], ay);
-        }
+        if (tail) table_add(T, slot, c, ax, ay);   // the run's totals
         if (DEBUG) {  // every beam learns the slot of its run (from the run's tail)
             const unsigned long long tm = __ballot(tail);
             const int mytail = lane + (int)__builtin_ctzll((tm >> lane) | (1ull << 63));
@@ -1012,49 +1078,13 @@ void k_assoc_group(const double* __restrict__ x, const int* __restrict__ boff, c
         ASSOC_TS(5);
 #endif
     }
-    // compact the used slots into the pose's place, slot order: its reserved one if the entries fit, else the front
-    // of its own beam range in the sparse area
-    const int room = (plan1 - plan0) + kStageSlack;
-    const bool fits = plan0 >= 0 && plan1 >= plan0 && plan1 <= nnz_total && nent <= room;   // (a stale plan is still a plan; a wild one is not)
-    const int sbase = fits ? plan0 + kStageSlack * (pose0 + tl) : sparse0 + j0;
-    int written = 0;
-    bool isnew = false;
-    for (int s0 = 0; s0 < kHash; s0 += kWave) {
-        const int s = s0 + lane;
-        const int k = T.key[s];
-        const bool occ = k != kEmpty;
-        const unsigned long long mask = __ballot(occ);
-        if (occ) {
-            const unsigned q = (unsigned)(written + prefix_count(mask, lane));   // (scalar bases + 32-bit offsets, like the beam loads)
-            *reinterpret_cast<int*>(reinterpret_cast<char*>(st_label + sbase) + (q << 2)) = k;
-            *reinterpret_cast<unsigned short*>(reinterpret_cast<char*>(st_k + sbase) + (q << 1)) = (unsigned short)T.cnt[s];   // (beams of one scan: <= B <= kMaxBeams)
-            *reinterpret_cast<double*>(reinterpret_cast<char*>(st_sbx + sbase) + (q << 3)) = T.sx[s];
-            *reinterpret_cast<double*>(reinterpret_cast<char*>(st_sby + sbase) + (q << 3)) = T.sy[s];
-            isnew |= k == -1;
-            if (DEBUG) T.owner[s] = q;
-        }
-        written += __popcll(mask);
-    }
-    const unsigned long long anynew = __ballot(isnew);
-    if (lane == 0) {
-        nent_out[tl] = written;
-        st_off[tl] = sbase;
-        isnew_out[tl] = anynew != 0ull;
-        // poses outside their reserved place: the host refreshes the plan when many (not counted while there is no plan
-        // at all -- the first sweep of a sequence: 100 000 atomics on one word)
-        if (!fits && plan1 > 0) atomicAdd(&flags[3], 1);
-
-        if (overflow) flags[0] = 1;
-    }
+    table_stage<DEBUG>(T, tl, j0, nent, overflow, plan0, plan1, nnz_total, pose0, sparse0, st_label, st_k, st_sbx,
+                       st_sby, nent_out, isnew_out, flags, st_off);
 #ifdef ICM_ASSOC_TS
     ASSOC_TS(6);
     ASSOC_TS_VAL(7, nbatch);
 #endif
-    if (DEBUG) {  // beam -> entry index within the pose
-        __builtin_amdgcn_wave_barrier();
-        __threadfence_block();
-        for (int j = j0 + lane; j < j1; j += kWave) bloc[j] = T.owner[bloc[j]];
-    }
+    if (DEBUG) table_remap(T, j0, j1, bloc);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1194,8 +1224,7 @@ void k_assoc_runs(const double* __restrict__ x, const int* __restrict__ roff, co
                   unsigned short* __restrict__ st_k, double* __restrict__ st_sbx, double* __restrict__ st_sby,
                   int* __restrict__ nent_out, int* __restrict__ isnew_out, int* __restrict__ flags, int nnz_total,
                   int* __restrict__ st_off, int pose0, int sparse0, unsigned long long* __restrict__ run_counts) {
-    constexpr int kHash = HS, kGroupCap = HS * 3 / 4;
-    constexpr int kHashShift = HS == 128 ? 25 : 24;
+    constexpr int kGroupCap = HS * 3 / 4;
     __shared__ PoseTable<HS> tables[kWavesPerBlock];
     const int lane = lane_id();
     // (one wave per pose, consecutive poses on consecutive workgroups: an XCD-contiguous order, eight resident waves and
@@ -1235,12 +1264,7 @@ void k_assoc_runs(const double* __restrict__ x, const int* __restrict__ roff, co
         const double kd = (double)(m.y & 0xffffu);
         c = make_double2(sb.x / kd, sb.y / kd);   // the circle's centre: the division k_run_build measured the radius against
     }
-    for (int s = lane; s < kHash; s += kWave) {
-        T.key[s] = kEmpty;
-        T.cnt[s] = 0;
-        T.sx[s] = 0.0;
-        T.sy[s] = 0.0;
-    }
+    table_clear(T);
     const float invf = (float)gp.inv;
     int nent = 0;
     bool overflow = false;
@@ -1270,27 +1294,12 @@ void k_assoc_runs(const double* __restrict__ x, const int* __restrict__ roff, co
         // settled runs claim / find the slot of their label (linear probing; a probe IS the compare-and-swap) and add
         // their cached totals by LDS atomics -- two runs of one landmark (seen left and right of an occluder, or
         // across the scan's wrap-around) need no arbitration
-        int slot = (int)(((unsigned)lab * 2654435761u) >> kHashShift);
+        int slot = table_home<HS>(lab);
         bool inserted = false, found = false;
-        if (settled) {
-            int held = atomicCAS(&T.key[slot], kEmpty, lab);
-            for (int probes = 0; probes < kHash; ++probes) {
-                if (held == kEmpty || held == lab) {
-                    inserted = held == kEmpty;
-                    found = true;
-                    break;
-                }
-                slot = (slot + 1) & (kHash - 1);
-                held = atomicCAS(&T.key[slot], kEmpty, lab);
-            }
-        }
+        if (settled) found = table_probe(T, lab, slot, table_cas(T, slot, lab), inserted);
         if (__ballot(settled && !found) != 0ull) overflow = true;
         nent += __popcll(__ballot(inserted));
-        if (settled && found) {
-            atomicAdd(&T.cnt[slot], k);
-            lds_add_f64(&T.sx[slot], sb.x);
-            lds_add_f64(&T.sy[slot], sb.y);
-        }
+        if (settled && found) table_add(T, slot, k, sb.x, sb.y);
         if (DEBUG && settled) {
             for (int i = 0; i < k; ++i) {
                 label[jr + i] = lab;
@@ -1312,22 +1321,9 @@ void k_assoc_runs(const double* __restrict__ x, const int* __restrict__ roff, co
                 const double wx = (b.x * ct - b.y * st) + px;
                 const double wy = (b.x * st + b.y * ct) + py;
                 bl = assoc_grid(g, gp, wx, wy, thr, thr2);
-                bs = (int)(((unsigned)bl * 2654435761u) >> kHashShift);
-                int held = atomicCAS(&T.key[bs], kEmpty, bl);
-                for (int probes = 0; probes < kHash; ++probes) {
-                    if (held == kEmpty || held == bl) {
-                        bins = held == kEmpty;
-                        bfound = true;
-                        break;
-                    }
-                    bs = (bs + 1) & (kHash - 1);
-                    held = atomicCAS(&T.key[bs], kEmpty, bl);
-                }
-                if (bfound) {
-                    atomicAdd(&T.cnt[bs], 1);
-                    lds_add_f64(&T.sx[bs], b.x);
-                    lds_add_f64(&T.sy[bs], b.y);
-                }
+                bs = table_home<HS>(bl);
+                bfound = table_probe(T, bl, bs, table_cas(T, bs, bl), bins);
+                if (bfound) table_add(T, bs, 1, b.x, b.y);
                 if (DEBUG) {
                     label[jj + lane] = bl;
                     bloc[jj + lane] = bs;
@@ -1352,47 +1348,14 @@ void k_assoc_runs(const double* __restrict__ x, const int* __restrict__ roff, co
         ASSOC_TS(5);
 #endif
     }
-    // compact the used slots into the pose's place, slot order (as k_assoc_group does)
-    const int room = (plan1 - plan0) + kStageSlack;
-    const bool fits = plan0 >= 0 && plan1 >= plan0 && plan1 <= nnz_total && nent <= room;
-    const int sbase = fits ? plan0 + kStageSlack * (pose0 + tl) : sparse0 + j0;
-    int written = 0;
-    bool isnew = false;
-    for (int s0 = 0; s0 < kHash; s0 += kWave) {
-        const int s = s0 + lane;
-        const int key = T.key[s];
-        const bool occ = key != kEmpty;
-        const unsigned long long mask = __ballot(occ);
-        if (occ) {
-            const unsigned q = (unsigned)(written + prefix_count(mask, lane));
-            *reinterpret_cast<int*>(reinterpret_cast<char*>(st_label + sbase) + (q << 2)) = key;
-            *reinterpret_cast<unsigned short*>(reinterpret_cast<char*>(st_k + sbase) + (q << 1)) = (unsigned short)T.cnt[s];
-            *reinterpret_cast<double*>(reinterpret_cast<char*>(st_sbx + sbase) + (q << 3)) = T.sx[s];
-            *reinterpret_cast<double*>(reinterpret_cast<char*>(st_sby + sbase) + (q << 3)) = T.sy[s];
-            isnew |= key == -1;
-            if (DEBUG) T.owner[s] = q;
-        }
-        written += __popcll(mask);
-    }
-    const unsigned long long anynew = __ballot(isnew);
-    if (lane == 0) {
-        nent_out[tl] = written;
-        st_off[tl] = sbase;
-        isnew_out[tl] = anynew != 0ull;
-        if (!fits && plan1 > 0) atomicAdd(&flags[3], 1);
-        if (overflow) flags[0] = 1;
-        if (run_counts && n_und) atomicAdd(&run_counts[1], (unsigned long long)n_und);   // (runs that went beam by beam: rare, counted over the handle's life)
-    }
+    table_stage<DEBUG>(T, tl, j0, nent, overflow, plan0, plan1, nnz_total, pose0, sparse0, st_label, st_k, st_sbx,
+                       st_sby, nent_out, isnew_out, flags, st_off);
+    if (lane == 0 && run_counts && n_und) atomicAdd(&run_counts[1], (unsigned long long)n_und);   // (runs that went beam by beam: rare, counted over the handle's life)
 #ifdef ICM_ASSOC_TS
     ASSOC_TS(6);
     ASSOC_TS_VAL(7, nbatch);
 #endif
-    if (DEBUG) {  // beam -> entry index within the pose
-        __builtin_amdgcn_wave_barrier();
-        __threadfence_block();
-        const int j1 = boff[tl + 1];
-        for (int j = j0 + lane; j < j1; j += kWave) bloc[j] = T.owner[bloc[j]];
-    }
+    if (DEBUG) table_remap(T, j0, boff[tl + 1], bloc);
 }
 
 // Running-mean term of one entry: sum of its beams' world points and their count.  One

@@ -661,7 +661,8 @@ def test_full_s2_in_four_processes_through_the_library_driver(tmp_path):
         assert np.array_equal(g["x2"], res[0]["x2"]) and np.array_equal(g["m2"], res[0]["m2"])
 
 
-def test_a_ghost_pose_is_solved_to_its_owners_value():
+@pytest.mark.parametrize("form", ["runs", "beams"])
+def test_a_ghost_pose_is_solved_to_its_owners_value(form):
     """A shard solves the pose in front of it too (its ghost pose) instead of receiving it between the colours: same
     beams, same neighbours' values, the same additions over its entries as its owner -- and targets that are the same
     running means up to the rounding of differently associated sums.  Directly: after one sweep, before any rank's
@@ -676,6 +677,7 @@ def test_a_ghost_pose_is_solved_to_its_owners_value():
     for r, (a, b) in enumerate(parts):
         e = SweepEngine(cfg)
         e.upload(wl.scans[a:b], wl.odometry, wl.u, t_begin=a, t_end=b, pose_major=True, ghost_scan=wl.scans[a - 1] if a else None)
+        e.set_assoc_form(form)
         run = ShardedSweep(e, r, world, wl.T, comm=NoComm(), stats=stats)
         stats = run.stats
         run.set_state(wl.map_init, wl.x_init, wl.x0)
