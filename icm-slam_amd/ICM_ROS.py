@@ -8,6 +8,7 @@ modified, the returned map is a fresh (2,K') array -- exactly the reference's co
 There is no CPU path: without the built library or without a GPU the calls raise.
 """
 import os
+import threading
 from copy import deepcopy as copy
 
 import numpy as np
@@ -15,6 +16,7 @@ import numpy as np
 from ICM_SLAM_tools import *  # noqa: F401,F403  (the reference star-imports its tools too)
 from ICM_SLAM_tools import ConfigICM, Mapa, ROS
 from icmslam_hip.engine import SweepEngine
+from sensors_definitions import Lidar, Odometria
 
 
 class ICM_ROS(ROS):
@@ -37,6 +39,20 @@ class ICM_ROS(ROS):
             else int(os.environ["ICMSLAM_DEVICE"])
         self._engine = None
         self._seq_key = None
+        # the two topic subscribers of the online mode (reference scripts/ICM_ROS.py:31-45): every message they parse
+        # calls principal_callback, which pairs scans and odometry by sequence number
+        D = {"config": config, "principalCallback": self.principal_callback}
+        self.lidar = Lidar(name="lidar", topic=getattr(config, "topic_laser", ""),
+                           topic_msg=getattr(config, "topic_laser_msg", ""), **D)
+        self.odom = Odometria(name="odometria", topic=getattr(config, "topic_odometry", ""),
+                              topic_msg=getattr(config, "topic_odometry_msg", ""), **D)
+        self._msg_lock = threading.Lock()   # callbacks may come from another thread than online_step
+        self._msg_read = [0, 0]             # messages of lidar / odom already looked at
+        self._pending = ({}, {})            # seq -> scan (B,1) / seq -> {'odo', 'u'} still without their partner
+        self._queue = []                    # complete samples (seq, scan (B,1), odo (3,1), u (2,1)), in seq order
+        self._last_seq = None               # seq of the last sample queued
+        self.dropped_samples = 0            # complete samples older than the last one queued (not processed)
+        self._online = None                 # the online pass running: the arrays pushed so far, chunk by chunk
 
     # ------------------------------------------------------------------------------------
     # data + initial state (ROS-free counterparts of inicializar_online)
@@ -47,6 +63,15 @@ class ICM_ROS(ROS):
         `observations` (B,T), `odometry` (3,T), `velocities` (2,T).  Ranges are inflated by
         the trunk radius and clipped like the Lidar callback does
         (reference scripts/sensors_definitions.py:22)."""
+        z, self.odometria, self.u = self.read_data_file(file)
+        self.mediciones = np.minimum(z + self.config.radio, z * 0.0 + self.config.rango_laser_max)
+        self.x0 = np.array([self.odometria[:, 0]]).T
+        self._seq_key = None
+        return self.mediciones, self.odometria, self.u
+
+    def read_data_file(self, file=None):
+        """The recorded arrays as stored (observations (B,T) before the Lidar callback's inflation, odometry (3,T),
+        velocities (2,T)) of `file` or `config.file`."""
         file = file or self.config.file
         cands = [file, os.path.join(os.path.dirname(os.path.abspath(__file__)), file)]
         path = next((c for c in cands if os.path.exists(c)), None)
@@ -61,13 +86,8 @@ class ICM_ROS(ROS):
         else:
             import scipy.io as sio
             d = sio.loadmat(path)
-        z = np.asarray(d["observations"], dtype=np.float64)
-        self.odometria = np.asarray(d["odometry"], dtype=np.float64)
-        self.u = np.asarray(d["velocities"], dtype=np.float64)
-        self.mediciones = np.minimum(z + self.config.radio, z * 0.0 + self.config.rango_laser_max)
-        self.x0 = np.array([self.odometria[:, 0]]).T
-        self._seq_key = None
-        return self.mediciones, self.odometria, self.u
+        return (np.asarray(d["observations"], dtype=np.float64), np.asarray(d["odometry"], dtype=np.float64),
+                np.asarray(d["velocities"], dtype=np.float64))
 
     def load_messages(self, lidar, odometria):
         """Sequence from the buffers of the two topic subscribers (`Lidar`, `Odometria` of
@@ -117,6 +137,101 @@ class ICM_ROS(ROS):
         yy = yy[:, :self.mapa_obj.landmarks_actuales]
         self.mapa_viejo = copy(yy)
         self.positions = copy(x)
+        self.iterations_flag = True
+
+    # ------------------------------------------------------------------------------------
+    # online initialisation (reference inicializar_online / principal_callback, scripts/ICM_ROS.py:47-119,
+    # scripts/ICM_SLAM.py:292-341): samples are paired as their messages arrive, pushed to the GPU and the causal pass
+    # resumes on them; online_finish() leaves the state inicializar_offline() leaves
+    # ------------------------------------------------------------------------------------
+    def principal_callback(self):
+        """Pair the messages of `self.lidar` and `self.odom` by sequence number and queue every complete sample in seq
+        order.  A sample that completes behind one already queued is dropped and counted (`dropped_samples`).  For an
+        in-order stream the queue holds exactly the samples load_messages() would build."""
+        with self._msg_lock:
+            for side, sensor in enumerate((self.lidar, self.odom)):
+                msgs = sensor.msgs
+                while self._msg_read[side] < len(msgs):
+                    m = msgs[self._msg_read[side]]
+                    self._msg_read[side] += 1
+                    seq = m['seq']
+                    other = self._pending[1 - side]
+                    if seq not in other:
+                        self._pending[side][seq] = m['data']
+                        continue
+                    partner = other.pop(seq)
+                    scan, odo = (m['data'], partner) if side == 0 else (partner, m['data'])
+                    if self._last_seq is not None and seq <= self._last_seq:
+                        self.dropped_samples += 1
+                        continue
+                    self._queue.append((seq, scan, odo['odo'], odo['u']))
+                    self._last_seq = seq
+                    self.seq = seq
+                    self.new_data += 1
+
+    def queued_samples(self):
+        """(mediciones (B,n), odometria (3,n), u (2,n)) of the samples queued and not yet pushed (None if none)."""
+        with self._msg_lock:
+            q = list(self._queue)
+        return self._stack(q)
+
+    @staticmethod
+    def _stack(q):
+        if not q:
+            return None
+        return (np.ascontiguousarray(np.concatenate([e[1].reshape(-1, 1) for e in q], axis=1), dtype=np.float64),
+                np.ascontiguousarray(np.concatenate([e[2].reshape(3, 1) for e in q], axis=1), dtype=np.float64),
+                np.ascontiguousarray(np.concatenate([e[3].reshape(2, 1) for e in q], axis=1), dtype=np.float64))
+
+    def icm_iterations_service(self, request, response):
+        """The `/icm_slam/iterative_flag` service (reference scripts/ICM_SLAM.py:292-299): ends the online phase."""
+        response['success'] = True
+        response['message'] = 'Working...'
+        self.iterations_flag = True
+        return True
+
+    def online_step(self):
+        """Push every queued sample to the GPU and run the causal pass over them: one push and one advance.  Returns the
+        number of samples processed (0: nothing was queued)."""
+        with self._msg_lock:
+            q, self._queue = self._queue, []
+        arrays = self._stack(q)
+        if arrays is None:
+            return 0
+        z, o, u = arrays
+        if self._online is None:
+            if self._engine is None:
+                self._engine = SweepEngine(self.config, self.device)
+            self._seq_key = None     # (the engine's uploaded sequence, if any, is dropped)
+            self.x0 = np.array([o[:, 0]]).T
+            self._engine.online_begin(z.shape[0], capacity=max(1024, z.shape[1]), x0=self.x0)
+            self._online = {"chunks": []}
+        self._online["chunks"].append(arrays)
+        self._engine.online_push(z, o, u)
+        self._engine.online_advance()
+        return z.shape[1]
+
+    def online_finish(self):
+        """End the online phase: Mapa.filtrar on the raw map, then `mapa_viejo`, `positions`, `mapa_obj`,
+        `mediciones` / `odometria` / `u` and `iterations_flag` as inicializar_offline() leaves them.  The engine keeps
+        the sequence, so the first iterations_process_offline does not upload it again."""
+        if self._online is None:
+            raise ValueError("online_finish: no sample has been processed (online_step)")
+        eng = self._engine
+        eng.online_finish()
+        x, y, cnt, lact, _ = eng.online_state()
+        chunks = self._online["chunks"]
+        self._online = None
+        self.mapa_obj = Mapa(self.config)
+        self.mapa_obj.landmarks_actuales = lact
+        self.mapa_obj.cant_obs_i = cnt
+        yy = self.mapa_obj.filtrar(y)
+        yy = yy[:, :self.mapa_obj.landmarks_actuales]
+        self.mapa_viejo = copy(yy)
+        self.positions = copy(x)
+        self.mediciones, self.odometria, self.u = (np.ascontiguousarray(np.concatenate([c[i] for c in chunks], axis=1))
+                                                   for i in range(3))
+        self.attach_engine(eng, self.mediciones, self.odometria, self.u)
         self.iterations_flag = True
 
     def inicializar_online(self):

@@ -175,8 +175,9 @@ class ROS:
 
 
 class Sensor:
-    """Message buffer of one ROS topic (reference scripts/ICM_SLAM_tools.py:343-449); kept so
-    that `Lidar`/`Odometria` definitions import, not used by the offline path."""
+    """Message buffer of one ROS topic (reference scripts/ICM_SLAM_tools.py:343-449): `Lidar` /
+    `Odometria` append parsed messages to `msgs` and call `principalCallback` (ICM_ROS.principal_callback
+    pairs them for the online initialisation)."""
 
     def __init__(self, config="", name="name", topic="", topic_msg="", principalCallback=""):
         self.msgs = []

@@ -42,12 +42,12 @@ std::string g_create_err;
 
 enum KernelId {
     KID_PREFILTER = 0, KID_SCAN, KID_ASSOC_BRUTE, KID_ASSOC_GROUP, KID_COMPACT, KID_SORT, KID_LM_BOUNDS, KID_LM_TOTALS,
-    KID_STATS_PREFIX, KID_LM_SCAN, KID_BEAM_TARGETS, KID_POSE_MOMENTS, KID_SOLVE, KID_FILTRAR, KID_NEIGH, KID_CHUNK_L1, KID_CHUNK_L2, KID_LM_L3, KID_REC_PUSH, KID_POSE_ROT, KID_ASSOC_RUNS, KID_RUN_BUILD, KID_COUNT
+    KID_STATS_PREFIX, KID_LM_SCAN, KID_BEAM_TARGETS, KID_POSE_MOMENTS, KID_SOLVE, KID_FILTRAR, KID_NEIGH, KID_CHUNK_L1, KID_CHUNK_L2, KID_LM_L3, KID_REC_PUSH, KID_POSE_ROT, KID_ASSOC_RUNS, KID_RUN_BUILD, KID_INIT_ADVANCE, KID_COUNT
 };
 const char* kKernelNames[KID_COUNT] = {"k_prefilter", "k_scan", "k_associate_brute", "k_assoc_group", "k_compact",
                                        "radix_sort_pairs", "k_lm_bounds", "k_lm_scan_totals", "k_stats_prefix",
                                        "k_lm_scan", "k_beam_targets", "k_pose_moments", "k_solve", "k_filtrar", "k_neigh_table",
-                                       "k_chunk_l1", "k_chunk_l2", "k_lm_l3", "k_rec_push", "k_pose_rot", "k_assoc_runs", "k_run_build"};
+                                       "k_chunk_l1", "k_chunk_l2", "k_lm_l3", "k_rec_push", "k_pose_rot", "k_assoc_runs", "k_run_build", "k_init_advance"};
 
 template <class T>
 struct DevBuf {
@@ -60,6 +60,22 @@ struct DevBuf {
         cap = 0;
         hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(n, 1) * sizeof(T));
         if (e == hipSuccess) cap = n;
+        return e;
+    }
+    // A reserve that KEEPS the first `keep` elements (a sequence growing in place, icm_online_push): the capacity at least
+    // doubles, the contents move by a device-to-device copy on `s`, and the old storage goes to `retired`, to be freed once
+    // the stream has passed the copy (hipFree would wait for the whole device here).
+    hipError_t grow(size_t n, size_t keep, hipStream_t s, std::vector<void*>& retired) {
+        if (n <= cap) return hipSuccess;
+        const size_t nc = std::max(n, 2 * cap);
+        T* q = nullptr;
+        hipError_t e = hipMalloc(reinterpret_cast<void**>(&q), nc * sizeof(T));
+        if (e != hipSuccess) return e;
+        keep = std::min(keep, cap);
+        if (p && keep) e = hipMemcpyAsync(q, p, keep * sizeof(T), hipMemcpyDeviceToDevice, s);
+        if (p) retired.push_back(p);
+        p = q;
+        cap = nc;
         return e;
     }
     void release() {
@@ -244,6 +260,13 @@ struct icm_handle {
     bool opt_req = false;      // asked for: by icm_sweep_classic for its first attempt, by icm_set_optimistic for the phase calls
     DevBuf<double> rot;   // (cos, sin)(theta - pi/2) per pose of the shard, refreshed at the start of every sweep (k_pose_rot)
     hipEvent_t ev_map = nullptr, ev_copied = nullptr;
+    // online initialisation (icm_online_*): a sequence that grows in place and the causal pass over it.  While it runs,
+    // odo / u are (3,on_cap) / (2,on_cap) (row stride = capacity), the per-scan buffers hold on_n scans and nloc = on_n.
+    bool online = false, on_finished = false, on_seeded = false;
+    int64_t on_cap = 0, on_n = 0, on_done = 0;   // capacity in samples, samples pushed, samples through the causal pass
+    DevBuf<double> on_x, on_y, on_cnt;            // poses (on_cap,3), running map (2,L), counts (L)
+    DevBuf<int> on_words, on_scan;                // [0] lact [1] overflow [2] samples finished; exclusive-scan scratch of a push
+    std::vector<void*> retired;                   // storage DevBuf::grow replaced (freed behind the next synchronisation)
     bool map_ev_in_local = false;   // this sweep's ev_map is the stop event of k_lm_l3 (icm_sweep_local)
     bool defer_filtrar = false;     // set by the library's own sweep drivers: Mapa.filtrar's launches are queued behind the solve launch (icm_sweep_targets)
     bool filtrar_deferred = false;  // ... and this sweep's are still to be queued
@@ -475,6 +498,8 @@ int icm_destroy(icm_handle* h) {
     if (h->solve_stream) { (void)hipStreamSynchronize(h->solve_stream); (void)hipStreamDestroy(h->solve_stream); }
     h->pre_x.release(); h->pre_y.release(); h->pre_n.release();
     h->rot.release(); h->st_off.release(); h->chunk_pub.release();
+    h->on_x.release(); h->on_y.release(); h->on_cnt.release(); h->on_words.release(); h->on_scan.release();
+    for (void* p : h->retired) (void)hipFree(p);
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
     return ICM_OK;
@@ -592,6 +617,7 @@ int icm_upload(icm_handle* h, const double* ranges, const double* odo, const dou
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->uploaded = true;
+    h->online = h->on_finished = h->on_seeded = false;
     h->ghost_uploaded = false;
     h->ghost_n = 0;
     h->snap.valid = false;
@@ -659,6 +685,8 @@ static int build_runs(icm_handle* h, const int* boff, const double2* bxy, int nl
     return ICM_OK;
 }
 
+static int prefilter_tail(icm_handle* h, int64_t* nnz_out);
+
 int icm_prefilter(icm_handle* h, int64_t* nnz_out) {
     if (!h) return ICM_ERR_ARG;
     if (!h->uploaded) FAIL(h, ICM_ERR_ARG, "icm_prefilter: call icm_upload first");
@@ -685,10 +713,20 @@ int icm_prefilter(icm_handle* h, int64_t* nnz_out) {
     HIPCHK(h, h->by.reserve(nz));
     HIPCHK(h, h->bxy.reserve(nz));
     HIPCHK(h, h->pose_s2.reserve(3 * (size_t)nloc));
+    TIMED(h, KID_PREFILTER, (k_prefilter<true><<<nb, kBlock, lds, h->stream>>>(h->ranges.p, h->cosb.p, h->sinb.p, nloc, B, h->cfg.rango_laser_max, h->cfg.dist_thr, nullptr, h->boff.p, h->bk.p, h->bd.p, h->bx.p, h->by.p, h->pose_s2.p, h->bxy.p, h->thr2, h->kmask.p)));
+    return prefilter_tail(h, nnz_out);
+}
+
+// Everything that follows once the kept beams of all nloc scans exist (nkept / boff / h_boff / nnz / bk .. bxy /
+// pose_s2): the geometric runs, the staging layout and the per-sweep buffers, the map buffers, the chunk plan, the
+// ghost scan of a shard.  icm_prefilter and icm_online_finish end here.
+static int prefilter_tail(icm_handle* h, int64_t* nnz_out) {
+    const int nloc = (int)h->nloc, B = (int)h->B;
+    const size_t lds = (size_t)B * kPrefilterLdsPerBeam;
+    const size_t nz = (size_t)std::max<int64_t>(h->nnz, 1);
     HIPCHK(h, h->pose_c.reserve(3 * (size_t)nloc));
     HIPCHK(h, h->pose_m.reserve(17 * (size_t)nloc));
     HIPCHK(h, h->rot.reserve(2 * (size_t)nloc));
-    TIMED(h, KID_PREFILTER, (k_prefilter<true><<<nb, kBlock, lds, h->stream>>>(h->ranges.p, h->cosb.p, h->sinb.p, nloc, B, h->cfg.rango_laser_max, h->cfg.dist_thr, nullptr, h->boff.p, h->bk.p, h->bd.p, h->bx.p, h->by.p, h->pose_s2.p, h->bxy.p, h->thr2, h->kmask.p)));
     // the geometric runs of every scan (k_assoc_runs associates runs, not beams): counted, scanned, filled
     {
         int rr = build_runs(h, h->boff.p, h->bxy.p, nloc, h->nrun, h->roff, h->r_s, h->r_m, &h->nruns);
@@ -788,8 +826,9 @@ int icm_prefilter(icm_handle* h, int64_t* nnz_out) {
 
 int icm_get_kept(icm_handle* h, int64_t* offsets, int32_t* beam_index, double* d, double* bx, double* by) {
     if (!h) return ICM_ERR_ARG;
-    if (!h->prefiltered) FAIL(h, ICM_ERR_ARG, "icm_get_kept: call icm_prefilter first");
+    if (!h->prefiltered && !h->online) FAIL(h, ICM_ERR_ARG, "icm_get_kept: call icm_prefilter (or icm_online_push) first");
     HIPCHK(h, hipSetDevice(h->device));
+    if (h->online) HIPCHK(h, hipStreamSynchronize(h->stream));   // (a push's second pre-filter pass may still be running)
     if (offsets)
         for (size_t i = 0; i <= (size_t)h->nloc; ++i) offsets[i] = h->h_boff[i];
     const size_t nz = (size_t)h->nnz;
@@ -835,6 +874,7 @@ static int upload_map(icm_handle* h) {
 // icm_sweep keeps them for the whole call and lets the copies run behind the queue.
 static int set_state_impl(icm_handle* h, const double* x, const double* x0, const double* map_in, int64_t K, int64_t lact_in, bool wait_host) {
     if (!h) return ICM_ERR_ARG;
+    if (h->online) FAIL(h, ICM_ERR_ARG, "icm_set_state: the online pass is running (icm_online_finish first)");
     if (!h->prefiltered) FAIL(h, ICM_ERR_ARG, "icm_set_state: call icm_upload + icm_prefilter first");
     if (!x || !x0 || (K > 0 && !map_in)) FAIL(h, ICM_ERR_ARG, "icm_set_state: null pointer");
     if (K < 0 || K > h->cfg.L || lact_in < 0) FAIL(h, ICM_ERR_ARG, "icm_set_state: K outside [0, L]");
@@ -2132,6 +2172,7 @@ static int sweep_without_upload(icm_handle* h, const double* xa, const double* x
 int icm_sweep(icm_handle* h, double* x, const double* x0, const double* map_in, int64_t K, int64_t lact_in,
               int schedule, double* map_out, double* counts_out, int64_t* K_out) {
     if (!h) return ICM_ERR_ARG;
+    if (h->online) FAIL(h, ICM_ERR_ARG, "icm_sweep: the online pass is running (icm_online_finish first)");
     int rc;
     const size_t T = (size_t)h->T;
     // A registered pose array (icm_pin_host): the solves mirror every pose they write into it (no download), and if it is
@@ -2456,7 +2497,7 @@ int icm_init_pass(icm_handle* h, const double* x0, double* y, double* counts, in
     HIPCHK(h, hipMemcpy(dc.p, counts, L * sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(h, hipMemcpy(di.p, hi, 2 * sizeof(int), hipMemcpyHostToDevice));
     InitArgs a;
-    a.x = dx.p; a.odo = h->odo.p; a.u = h->u.p; a.T = (int)T; a.boff = h->boff.p; a.bx = h->bx.p; a.by = h->by.p;
+    a.x = dx.p; a.odo = h->odo.p; a.u = h->u.p; a.T = (int)T; a.ld = (int)T; a.t_first = 1; a.boff = h->boff.p; a.bx = h->bx.p; a.by = h->by.p;
     a.y = dy.p; a.cnt = dc.p; a.lact = di.p; a.L = (int)L; a.maxb = maxb; a.thr = h->cfg.dist_thr;
     a.dt = h->cfg.deltat; a.R0 = h->cfg.R[0]; a.R1 = h->cfg.R[1]; a.R2 = h->cfg.R[2];
     a.Q0 = h->cfg.Q[0]; a.Q1 = h->cfg.Q[1]; a.cte = h->cfg.cte_odom; a.flags = di.p + 1;
@@ -2475,6 +2516,253 @@ int icm_init_pass(icm_handle* h, const double* x0, double* y, double* counts, in
         x_out[t] = xt[3 * t];
         x_out[T + t] = xt[3 * t + 1];
         x_out[2 * T + t] = xt[3 * t + 2];
+    }
+    return ICM_OK;
+}
+
+// ---- online initialisation ---------------------------------------------------------------------
+// The sequence grows in place (icm_online_push) and the causal pass resumes where it stopped (icm_online_advance,
+// k_init_advance); icm_online_finish turns what was pushed into the handle's sweep sequence.
+
+static void free_retired(icm_handle* h) {   // (call only behind a synchronisation of h->stream)
+    for (void* p : h->retired) (void)hipFree(p);
+    h->retired.clear();
+}
+
+// Room for `need` samples in every per-sample buffer, the capacity at least doubling; odo / u change row stride.
+static int online_reserve(icm_handle* h, int64_t need) {
+    if (need <= h->on_cap) return ICM_OK;
+    const size_t nc = (size_t)std::max<int64_t>(need, 2 * h->on_cap), n = (size_t)h->on_n, B = (size_t)h->B;
+    const size_t words = (B + kWave - 1) / kWave;
+    auto& rt = h->retired;
+    hipStream_t s = h->stream;
+    for (DevBuf<double>* rows : {&h->odo, &h->u}) {
+        const size_t nrow = rows == &h->odo ? 3 : 2;
+        double* q = nullptr;
+        HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&q), nrow * nc * sizeof(double)));
+        if (rows->p && n) HIPCHK(h, hipMemcpy2DAsync(q, nc * sizeof(double), rows->p, (size_t)h->on_cap * sizeof(double), n * sizeof(double), nrow, hipMemcpyDeviceToDevice, s));
+        if (rows->p) rt.push_back(rows->p);
+        rows->p = q;
+        rows->cap = nrow * nc;
+    }
+    HIPCHK(h, h->ranges.grow(nc * B, n * B, s, rt));
+    HIPCHK(h, h->nkept.grow(nc + 1, n, s, rt));
+    HIPCHK(h, h->boff.grow(nc + 1, n + 1, s, rt));
+    HIPCHK(h, h->kmask.grow(nc * words, n * words, s, rt));
+    HIPCHK(h, h->pose_s2.grow(3 * nc, 3 * n, s, rt));
+    HIPCHK(h, h->on_x.grow(3 * nc, 3 * (size_t)h->on_done, s, rt));
+    HIPCHK(h, h->on_scan.grow(nc + 1, 0, s, rt));
+    h->on_cap = (int64_t)nc;
+    return ICM_OK;
+}
+
+int icm_online_begin(icm_handle* h, const double* cosb, const double* sinb, int64_t B, int64_t capacity_hint) {
+    if (!h) return ICM_ERR_ARG;
+    if (!cosb || !sinb) FAIL(h, ICM_ERR_ARG, "icm_online_begin: null pointer");
+    if (h->world > 1) FAIL(h, ICM_ERR_ARG, "icm_online_begin: the online pass is one chain on one GPU (this handle is a shard)");
+    if (B < 1) FAIL(h, ICM_ERR_ARG, "icm_online_begin: bad B");
+    if (B > ICM_MAX_BEAMS)
+        FAIL(h, ICM_ERR_UNSUPPORTED, "icm_online_begin: B = " + std::to_string(B) + " beams per scan; the scan pre-filter stages at most ICM_MAX_BEAMS = " +
+                                         std::to_string(ICM_MAX_BEAMS) + " (4 waves x B x 28 bytes of LDS per workgroup)");
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    free_retired(h);
+    // drop the uploaded sequence and any online state, as icm_upload does
+    h->uploaded = h->prefiltered = h->have_state = false;
+    h->ghost_uploaded = false;
+    h->ghost_n = 0;
+    h->snap.valid = false;
+    h->online = true;
+    h->on_finished = h->on_seeded = false;
+    h->T = 0; h->B = B; h->t_begin = 0; h->nloc = 0; h->nnz = 0;
+    h->on_cap = h->on_n = h->on_done = 0;
+    h->h_boff.assign(1, 0);
+    // fresh storage: what a previous sequence left is not kept
+    h->odo.release(); h->u.release();
+    HIPCHK(h, h->cosb.reserve((size_t)B));
+    HIPCHK(h, h->sinb.reserve((size_t)B));
+    HIPCHK(h, hipMemcpyAsync(h->cosb.p, cosb, (size_t)B * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->sinb.p, sinb, (size_t)B * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    const size_t L = (size_t)h->cfg.L;
+    HIPCHK(h, h->on_y.reserve(2 * L)); HIPCHK(h, h->on_cnt.reserve(L)); HIPCHK(h, h->on_words.reserve(4));
+    {
+        int rc = online_reserve(h, std::max<int64_t>(capacity_hint, 1));
+        if (rc) return rc;
+    }
+    HIPCHK(h, hipMemsetAsync(h->boff.p, 0, sizeof(int), h->stream));
+    const size_t lds = (size_t)B * kPrefilterLdsPerBeam;
+    HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_prefilter<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_prefilter<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_init_advance), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)((size_t)B * (4 * sizeof(double) + sizeof(int)))));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return ICM_OK;
+}
+
+int icm_online_push(icm_handle* h, const double* ranges, const double* odo, const double* u, int64_t n, int64_t* nnz_out) {
+    if (!h) return ICM_ERR_ARG;
+    if (!h->online) FAIL(h, ICM_ERR_ARG, h->on_finished ? "icm_online_push: the online pass has been finished (icm_online_begin starts a new one)"
+                                                        : "icm_online_push: call icm_online_begin first");
+    if (n < 0 || (n > 0 && (!ranges || !odo || !u))) FAIL(h, ICM_ERR_ARG, "icm_online_push: null pointer or n < 0");
+    const int64_t t0 = h->on_n, B = h->B;
+    if (t0 + n > (1 << 30) || (t0 + n) * B > (int64_t)2000000000) FAIL(h, ICM_ERR_UNSUPPORTED, "icm_online_push: sequence too large for 32-bit beam indices");
+    if (n == 0) {
+        if (nnz_out) *nnz_out = h->nnz;
+        return ICM_OK;
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    {
+        int rc = online_reserve(h, t0 + n);
+        if (rc) return rc;
+    }
+    const size_t cap = (size_t)h->on_cap, words = (size_t)((B + kWave - 1) / kWave);
+    HIPCHK(h, hipMemcpyAsync(h->ranges.p + (size_t)t0 * B, ranges, (size_t)(n * B) * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpy2DAsync(h->odo.p + t0, cap * sizeof(double), odo, (size_t)n * sizeof(double), (size_t)n * sizeof(double), 3, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpy2DAsync(h->u.p + t0, cap * sizeof(double), u, (size_t)n * sizeof(double), (size_t)n * sizeof(double), 2, hipMemcpyHostToDevice, h->stream));
+    // filtrar_z of the new scans: the same two passes as icm_prefilter, on the slice; offsets rebased behind boff[t0]
+    const double* rs = h->ranges.p + (size_t)t0 * B;
+    const int nb = nblocks_waves(n), Bi = (int)B;
+    const size_t lds = (size_t)B * kPrefilterLdsPerBeam;
+    unsigned long long* km = h->kmask.p + (size_t)t0 * words;
+    TIMED(h, KID_PREFILTER, (k_prefilter<false><<<nb, kBlock, lds, h->stream>>>(rs, h->cosb.p, h->sinb.p, (int)n, Bi, h->cfg.rango_laser_max, h->cfg.dist_thr, h->nkept.p + t0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, h->thr2, km)));
+    k_exscan_i32<<<1, 1024, 0, h->stream>>>(h->nkept.p + t0, h->on_scan.p, (int)n);
+    k_rebase_offsets<<<nblocks_threads(n), kBlock, 0, h->stream>>>(h->on_scan.p, (int)n, h->boff.p + t0);
+    HIPCHK(h, hipGetLastError());
+    h->h_boff.resize((size_t)(t0 + n) + 1);
+    HIPCHK(h, hipMemcpyAsync(h->h_boff.data() + t0, h->boff.p + t0, ((size_t)n + 1) * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));   // the one wait of a push: how many beams the new scans keep
+    free_retired(h);
+    const int64_t nnz_old = h->nnz, nnz = h->h_boff[(size_t)(t0 + n)];
+    auto& rt = h->retired;
+    const size_t nz = (size_t)std::max<int64_t>(nnz, 1), keep = (size_t)nnz_old;
+    HIPCHK(h, h->bk.grow(nz, keep, h->stream, rt));
+    HIPCHK(h, h->bd.grow(nz, keep, h->stream, rt));
+    HIPCHK(h, h->bx.grow(nz, keep, h->stream, rt));
+    HIPCHK(h, h->by.grow(nz, keep, h->stream, rt));
+    HIPCHK(h, h->bxy.grow(nz, keep, h->stream, rt));
+    TIMED(h, KID_PREFILTER, (k_prefilter<true><<<nb, kBlock, lds, h->stream>>>(rs, h->cosb.p, h->sinb.p, (int)n, Bi, h->cfg.rango_laser_max, h->cfg.dist_thr, nullptr, h->boff.p + t0, h->bk.p, h->bd.p, h->bx.p, h->by.p, h->pose_s2.p + 3 * (size_t)t0, h->bxy.p, h->thr2, km)));
+    HIPCHK(h, hipGetLastError());
+    h->on_n = t0 + n;
+    h->nloc = h->on_n;
+    h->nnz = nnz;
+    if (nnz_out) *nnz_out = nnz;
+    return ICM_OK;
+}
+
+int icm_online_seed(icm_handle* h, const double* x0, const double* y, const double* counts, int64_t lact) {
+    if (!h) return ICM_ERR_ARG;
+    if (!h->online) FAIL(h, ICM_ERR_ARG, "icm_online_seed: call icm_online_begin first");
+    if (h->on_n < 1) FAIL(h, ICM_ERR_ARG, "icm_online_seed: push scan 0 first (the map is seeded from its clusters)");
+    if (!x0 || !y || !counts) FAIL(h, ICM_ERR_ARG, "icm_online_seed: null pointer");
+    const size_t L = (size_t)h->cfg.L;
+    if (lact <= 0 || lact > (int64_t)L) FAIL(h, ICM_ERR_ARG, "icm_online_seed: seed the map with the first scan's clusters (icm_cluster_first_scan)");
+    HIPCHK(h, hipSetDevice(h->device));
+    const int w[3] = {(int)lact, 0, 1};
+    HIPCHK(h, hipMemcpyAsync(h->on_x.p, x0, 3 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->on_y.p, y, 2 * L * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->on_cnt.p, counts, L * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->on_words.p, w, 3 * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->on_done = 1;
+    h->on_seeded = true;
+    return ICM_OK;
+}
+
+int icm_online_advance(icm_handle* h, int64_t t_end, double* x_new, int64_t* lact_out) {
+    if (!h) return ICM_ERR_ARG;
+    if (!h->online) FAIL(h, ICM_ERR_ARG, "icm_online_advance: no online pass is running (icm_online_begin)");
+    if (!h->on_seeded) FAIL(h, ICM_ERR_ARG, "icm_online_advance: seed the map first (icm_online_seed)");
+    if (t_end > h->on_n) FAIL(h, ICM_ERR_ARG, "icm_online_advance: t_end = " + std::to_string(t_end) + " is past the " + std::to_string(h->on_n) + " samples pushed");
+    if (t_end < h->on_done) FAIL(h, ICM_ERR_ARG, "icm_online_advance: t_end = " + std::to_string(t_end) + " is behind the " + std::to_string(h->on_done) + " samples already processed");
+    const int64_t t_first = h->on_done, n = t_end - t_first;
+    if (n > 0 && !x_new) FAIL(h, ICM_ERR_ARG, "icm_online_advance: null pointer");
+    HIPCHK(h, hipSetDevice(h->device));
+    int w[3] = {0, 0, (int)t_first};
+    std::vector<double> xr((size_t)std::max<int64_t>(3 * n, 1));
+    if (n > 0) {
+        InitArgs a;
+        a.x = h->on_x.p; a.odo = h->odo.p; a.u = h->u.p; a.T = (int)t_end; a.ld = (int)h->on_cap; a.t_first = (int)t_first;
+        a.boff = h->boff.p; a.bx = h->bx.p; a.by = h->by.p;
+        a.y = h->on_y.p; a.cnt = h->on_cnt.p; a.lact = h->on_words.p; a.L = (int)h->cfg.L; a.maxb = (int)h->B; a.thr = h->cfg.dist_thr;
+        a.dt = h->cfg.deltat; a.R0 = h->cfg.R[0]; a.R1 = h->cfg.R[1]; a.R2 = h->cfg.R[2];
+        a.Q0 = h->cfg.Q[0]; a.Q1 = h->cfg.Q[1]; a.cte = h->cfg.cte_odom; a.flags = h->on_words.p + 1;
+        const size_t lds = (size_t)h->B * (4 * sizeof(double) + sizeof(int));
+        HIPCHK(h, hipMemsetAsync(h->on_words.p + 1, 0, sizeof(int), h->stream));
+        TIMED(h, KID_INIT_ADVANCE, (k_init_advance<<<1, kWave, lds, h->stream>>>(a)));
+        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, hipMemcpyAsync(xr.data(), h->on_x.p + 3 * (size_t)t_first, 3 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHK(h, hipMemcpyAsync(w, h->on_words.p, 3 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    free_retired(h);
+    const int64_t t_fin = n > 0 ? w[2] : t_first;
+    for (int64_t i = 0; i < t_fin - t_first; ++i) {
+        x_new[i] = xr[3 * (size_t)i];
+        x_new[n + i] = xr[3 * (size_t)i + 1];
+        x_new[2 * n + i] = xr[3 * (size_t)i + 2];
+    }
+    h->on_done = t_fin;
+    if (lact_out) *lact_out = w[0];
+    if (n > 0 && w[1])
+        FAIL(h, ICM_ERR_INDEX, "online pass: a new landmark at sample " + std::to_string(t_fin) +
+                                   " exceeds the map capacity L (the reference raises IndexError, scripts/ICM_SLAM_tools.py:191)");
+    return ICM_OK;
+}
+
+int icm_online_state(icm_handle* h, double* x, double* y, double* counts, int64_t* lact, int64_t* t_done) {
+    if (!h) return ICM_ERR_ARG;
+    if (!h->on_seeded) FAIL(h, ICM_ERR_ARG, "icm_online_state: no seeded online pass (icm_online_begin, icm_online_push, icm_online_seed)");
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t n = (size_t)h->on_done, L = (size_t)h->cfg.L;
+    std::vector<double> xr(x ? 3 * n : 0);
+    int w[3] = {0, 0, 0};
+    if (x) HIPCHK(h, hipMemcpyAsync(xr.data(), h->on_x.p, 3 * n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (y) HIPCHK(h, hipMemcpyAsync(y, h->on_y.p, 2 * L * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (counts) HIPCHK(h, hipMemcpyAsync(counts, h->on_cnt.p, L * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(w, h->on_words.p, 3 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (x)
+        for (size_t t = 0; t < n; ++t) {
+            x[t] = xr[3 * t];
+            x[n + t] = xr[3 * t + 1];
+            x[2 * n + t] = xr[3 * t + 2];
+        }
+    if (lact) *lact = w[0];
+    if (t_done) *t_done = (int64_t)n;
+    return ICM_OK;
+}
+
+int icm_online_finish(icm_handle* h) {
+    if (!h) return ICM_ERR_ARG;
+    if (!h->online) FAIL(h, ICM_ERR_ARG, h->on_finished ? "icm_online_finish: already finished" : "icm_online_finish: call icm_online_begin first");
+    if (h->on_n < 2) FAIL(h, ICM_ERR_ARG, "icm_online_finish: a sweep sequence needs at least 2 samples");
+    HIPCHK(h, hipSetDevice(h->device));
+    const int64_t T = h->on_n;
+    // odo / u: (3,T) / (2,T), as icm_upload lays them out
+    if (h->on_cap != T) {
+        for (DevBuf<double>* rows : {&h->odo, &h->u}) {
+            const size_t nrow = rows == &h->odo ? 3 : 2;
+            DevBuf<double> q;
+            HIPCHK(h, q.reserve(nrow * (size_t)T));
+            HIPCHK(h, hipMemcpy2DAsync(q.p, (size_t)T * sizeof(double), rows->p, (size_t)h->on_cap * sizeof(double), (size_t)T * sizeof(double), nrow, hipMemcpyDeviceToDevice, h->stream));
+            h->retired.push_back(rows->p);
+            *rows = q;
+        }
+    }
+    HIPCHK(h, h->odo_cs.reserve(2 * (size_t)T));
+    HIPCHK(h, h->pose_cs.reserve(2 * (size_t)T));
+    k_odo_trig<<<nblocks_threads(T), kBlock, 0, h->stream>>>(h->odo.p, (int)T, h->odo_cs.p);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    free_retired(h);
+    h->T = T; h->nloc = T; h->t_begin = 0;
+    h->online = false;
+    h->on_finished = true;
+    h->uploaded = true;
+    int rc = prefilter_tail(h, nullptr);
+    if (rc) {
+        h->uploaded = false;
+        return rc;
     }
     return ICM_OK;
 }

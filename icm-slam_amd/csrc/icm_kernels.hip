@@ -28,6 +28,7 @@
 //                              ONE LANE per pose, everything in registers
 //             k_solve_* (wave per pose, per-beam / per-entry energy): cross-checks
 //   init      k_init_pass      the causal initialisation pass (one wave walks the sequence)
+//             k_init_advance   its resumable form: the samples pushed since the last launch (online initialisation)
 //
 // Mapping: phase A one wavefront per pose (lanes over its runs / its kept beams), entry kernels one DPP
 // row (16 lanes) per pose, landmark kernels one wavefront per landmark, solves one lane per
@@ -3339,10 +3340,12 @@ __global__ __launch_bounds__(kWave) void k_solve_sequential(SolveArgs a) {
 // LDS per scan: label, world point and target of every kept beam.
 // ---------------------------------------------------------------------------------------
 struct InitArgs {
-    double* x;  // (T,3); x[0] = x0 on entry
-    const double* odo;
-    const double* u;
-    int T;
+    double* x;  // (rows,3); x[t_first - 1] holds the pose the chain starts from (x[0] = x0 for k_init_pass)
+    const double* odo;   // (3,ld)
+    const double* u;     // (2,ld)
+    int T;      // k_init_pass: poses of the sequence; k_init_advance: t_end (samples t_first..T-1 are processed)
+    int ld;     // row stride of odo / u: T for an uploaded sequence, the capacity of the online buffers otherwise
+    int t_first;   // k_init_advance: first sample to process (>= 1)
     const int* boff;
     const double *bx, *by;
     double* y;    // (2,L) running map, in/out
@@ -3350,134 +3353,209 @@ struct InitArgs {
     int* lact;    // landmarks in use, in/out
     int L, maxb;
     double thr, dt, R0, R1, R2, Q0, Q1, cte;
-    int* flags;   // [0] = a new landmark would not fit in L (the reference raises IndexError)
+    int* flags;   // [0] = a new landmark would not fit in L (the reference raises IndexError);
+                  // k_init_advance: [1] = samples finished (the failing sample t, or T)
 };
 
+// LDS of one scan: world point, target and label of every kept beam (maxb of them).
+struct InitLds {
+    double *wx, *wy, *tx, *ty;
+    int* lab;
+};
+__device__ __forceinline__ InitLds init_lds(unsigned char* smem, int maxb) {
+    InitLds s;
+    s.wx = reinterpret_cast<double*>(smem);
+    s.wy = s.wx + maxb;
+    s.tx = s.wy + maxb;
+    s.ty = s.tx + maxb;
+    s.lab = reinterpret_cast<int*>(s.ty + maxb);
+    return s;
+}
+
+// Predict pose t with the unicycle model from xt = pose t-1.
+__device__ __forceinline__ void init_predict(const InitArgs& a, int t, const double xt[3], double xc[3]) {
+    const double v = a.u[t - 1], w = a.u[(size_t)a.ld + t - 1];
+    xc[0] = xt[0] + a.dt * (cos(xt[2]) * v);
+    xc[1] = xt[1] + a.dt * (sin(xt[2]) * v);
+    xc[2] = xt[2] + a.dt * w;
+}
+
+// Associate the n kept beams of the scan (from j0) against the running map, brute force like the reference's
+// cdist / argmin, projected with the predicted pose; every gated-out beam shares ONE new label.  false: that label
+// would not fit in L (nothing global has been written).
+__device__ __forceinline__ bool init_associate(const InitArgs& a, int j0, int n, const double xc[3], double ct, double st,
+                                               int& lact, const InitLds& s, int lane) {
+    bool isnew = false;
+    for (int j = lane; j < n; j += kWave) {
+        const double bxx = a.bx[j0 + j], byy = a.by[j0 + j];
+        const double wx = (bxx * ct - byy * st) + xc[0], wy = (bxx * st + byy * ct) + xc[1];
+        double best = __builtin_huge_val();
+        int bid = -1;
+        for (int i = 0; i < lact; ++i) {
+            const double dx = a.y[i] - wx, dy = a.y[a.L + i] - wy;
+            const double d = sqrt(dx * dx + dy * dy);
+            if (d < best) {
+                best = d;
+                bid = i;
+            }
+        }
+        const int lab = (bid >= 0 && !(best > a.thr)) ? bid : -1;
+        isnew |= lab < 0;
+        s.wx[j] = wx;
+        s.wy[j] = wy;
+        s.lab[j] = lab;
+    }
+    if (__ballot(isnew) != 0ull) {  // all gated-out beams of the scan share ONE new label
+        if (lact >= a.L) return false;
+        for (int j = lane; j < n; j += kWave)
+            if (s.lab[j] < 0) s.lab[j] = lact;
+        ++lact;
+    }
+    __builtin_amdgcn_wave_barrier();
+    return true;
+}
+
+// Fold the scan into the running means (the first beam of each label sums its group), then gather every beam's
+// target y[:, c] after the update (scripts/ICM_ROS.py:117-118).
+__device__ __forceinline__ void init_fold(const InitArgs& a, int n, const InitLds& s, int lane) {
+    for (int j = lane; j < n; j += kWave) {
+        const int lab = s.lab[j];
+        bool leader = true;
+        for (int q = 0; q < j; ++q) leader &= s.lab[q] != lab;
+        if (leader) {
+            double sx = 0.0, sy = 0.0;
+            int k = 0;
+            for (int q = j; q < n; ++q)
+                if (s.lab[q] == lab) {
+                    sx += s.wx[q];
+                    sy += s.wy[q];
+                    ++k;
+                }
+            const double nn = a.cnt[lab], tot = nn + (double)k;
+            a.y[lab] = sx / tot + a.y[lab] * nn / tot;
+            a.y[a.L + lab] = sy / tot + a.y[a.L + lab] * nn / tot;
+            a.cnt[lab] = tot;
+        }
+    }
+    __threadfence_block();
+    for (int j = lane; j < n; j += kWave) {
+        s.tx[j] = a.y[s.lab[j]];
+        s.ty[j] = a.y[a.L + s.lab[j]];
+    }
+    __builtin_amdgcn_wave_barrier();
+}
+
+// The one-sided solve (fun_x / minimizar_x, scripts/ICM_ROS.py:254-278) in the moment form the sweeps use (round 4;
+// the per-beam sum with a wave reduction per evaluation took 52 us per pose): the wave forms the pose's 14 sums
+// once, about the prediction (the Nelder-Mead's start), one term per beam (an entry of one beam: no scatter
+// term); then the folded energy, every lane running the same chain on the same numbers.  xt: pose t-1 in, pose t out.
+__device__ __forceinline__ void init_solve(const InitArgs& a, int t, int j0, int n, const double xc[3], double ct, double st,
+                                           const InitLds& s, double xt[3], int lane) {
+    PoseIn in;
+    in.n = n;
+    in.ua0 = a.u[t - 1]; in.ua1 = a.u[(size_t)a.ld + t - 1]; in.ut0 = in.ut1 = 0.0;
+    load3(a.odo, a.ld, t - 1, in.oa);
+    load3(a.odo, a.ld, t, in.ot);
+    in.op[0] = in.op[1] = in.op[2] = 0.0;
+    in.coa = cos(in.oa[2]); in.soa = sin(in.oa[2]); in.cot = 1.0; in.sot = 0.0;
+    in.pox = xc[0]; in.poy = xc[1]; in.tho = xc[2]; in.co = cos(xc[2]); in.so = sin(xc[2]);
+    {
+        double m[kMomentCount];
+#pragma unroll
+        for (int q = 0; q < kMomentCount; ++q) m[q] = 0.0;
+        for (int j = lane; j < n; j += kWave) {
+            const double bxx = a.bx[j0 + j], byy = a.by[j0 + j];
+            const double wx = ct * bxx - st * byy, wy = st * bxx + ct * byy;
+            const double rx = (xc[0] + wx) - s.tx[j], ry = (xc[1] + wy) - s.ty[j];
+            m[0] += 1.0; m[1] += wx; m[2] += wy; m[3] += rx; m[4] += ry;
+            m[5] += wx * wx; m[6] += wy * wy; m[7] += wx * wy;
+            m[8] += wx * rx; m[9] += wy * rx; m[10] += wx * ry; m[11] += wy * ry;
+            m[12] += rx * rx; m[13] += ry * ry;
+        }
+#pragma unroll
+        for (int q = 0; q < kMomentCount; ++q) in.pm[q] = wave_sum(m[q]);
+        in.pm[14] = in.pm[15] = in.pm[16] = 0.0;
+    }
+    SolveArgs sa;
+    sa.x = a.x; sa.x0 = nullptr; sa.odo = a.odo; sa.u = a.u;
+    sa.T = t + 1;   // (one-sided: pose t is the last one there is)
+    sa.t_begin = 0; sa.nloc = a.T;
+    sa.dt = a.dt; sa.R0 = a.R0; sa.R1 = a.R1; sa.R2 = a.R2; sa.Q0 = a.Q0; sa.Q1 = a.Q1; sa.cte = a.cte;
+    sa.diag = nullptr; sa.rot = nullptr; sa.cs = nullptr; sa.odo_cs = nullptr; sa.epoch = 0; sa.xh = nullptr;
+    sa.ghost_n = 0; sa.ghost_m = nullptr;
+    double r0 = 0.0, r1 = 0.0, r2 = 0.0;
+    const bool iso = a.Q0 == a.Q1 && a.R0 == a.R1;
+    bool ok = false;
+    if (iso) ok = solve_pose_in<true>(sa, t, in, xt, false, r0, r1, r2);
+    if (!ok) solve_pose_in<false>(sa, t, in, xt, false, r0, r1, r2);
+    xt[0] = r0; xt[1] = r1; xt[2] = r2;
+}
+
+// One sample of the causal chain: predict, associate, fold, moments, solve; xt = pose t-1 in, pose t out (written to
+// x[t]).  false: a new landmark would not fit in L -- xt, x[t], the map and lact are left as they were.
+__device__ __forceinline__ bool init_step(const InitArgs& a, int t, double xt[3], int& lact, const InitLds& s, int lane) {
+    double xc[3];
+    init_predict(a, t, xt, xc);
+    const int j0 = a.boff[t], n = a.boff[t + 1] - j0;
+    if (n == 0) {  // no observation: keep the prediction (scripts/ICM_ROS.py:110-113)
+        xt[0] = xc[0]; xt[1] = xc[1]; xt[2] = xc[2];
+    } else {
+        double ct, st;
+        pose_rot(xc[2], ct, st);
+        if (!init_associate(a, j0, n, xc, ct, st, lact, s, lane)) return false;
+        init_fold(a, n, s, lane);
+        init_solve(a, t, j0, n, xc, ct, st, s, xt, lane);
+    }
+    if (lane == 0) {
+        a.x[3 * (size_t)t] = xt[0];
+        a.x[3 * (size_t)t + 1] = xt[1];
+        a.x[3 * (size_t)t + 2] = xt[2];
+    }
+    return true;
+}
+
+// The whole uploaded sequence, t = 1..T-1 (icm_init_pass).  LDS: the sequence's largest kept-beam count.
 __global__ __launch_bounds__(kWave) void k_init_pass(InitArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];
-    double* lwx = reinterpret_cast<double*>(smem);
-    double* lwy = lwx + a.maxb;
-    double* ltx = lwy + a.maxb;
-    double* lty = ltx + a.maxb;
-    int* llab = reinterpret_cast<int*>(lty + a.maxb);
+    const InitLds s = init_lds(smem, a.maxb);
     const int lane = lane_id();
     int lact = *a.lact;
     double xt[3] = {a.x[0], a.x[1], a.x[2]};
-    for (int t = 1; t < a.T; ++t) {
-        const double v = a.u[t - 1], w = a.u[(size_t)a.T + t - 1];
-        const double xc0 = xt[0] + a.dt * (cos(xt[2]) * v), xc1 = xt[1] + a.dt * (sin(xt[2]) * v), xc2 = xt[2] + a.dt * w;
-        const int j0 = a.boff[t], n = a.boff[t + 1] - j0;
-        if (n == 0) {  // no observation: keep the prediction (scripts/ICM_ROS.py:110-113)
-            xt[0] = xc0; xt[1] = xc1; xt[2] = xc2;
-        } else {
-            double ct, st;
-            pose_rot(xc2, ct, st);
-            bool isnew = false;
-            for (int j = lane; j < n; j += kWave) {
-                const double bxx = a.bx[j0 + j], byy = a.by[j0 + j];
-                const double wx = (bxx * ct - byy * st) + xc0, wy = (bxx * st + byy * ct) + xc1;
-                double best = __builtin_huge_val();
-                int bid = -1;
-                for (int i = 0; i < lact; ++i) {
-                    const double dx = a.y[i] - wx, dy = a.y[a.L + i] - wy;
-                    const double d = sqrt(dx * dx + dy * dy);
-                    if (d < best) {
-                        best = d;
-                        bid = i;
-                    }
-                }
-                const int lab = (bid >= 0 && !(best > a.thr)) ? bid : -1;
-                isnew |= lab < 0;
-                lwx[j] = wx;
-                lwy[j] = wy;
-                llab[j] = lab;
-            }
-            if (__ballot(isnew) != 0ull) {  // all gated-out beams of the scan share ONE new label
-                if (lact >= a.L) {
-                    if (lane == 0) a.flags[0] = 1;
-                    break;
-                }
-                for (int j = lane; j < n; j += kWave)
-                    if (llab[j] < 0) llab[j] = lact;
-                ++lact;
-            }
-            __builtin_amdgcn_wave_barrier();
-            // fold the scan into the running means: the first beam of each label sums its group
-            for (int j = lane; j < n; j += kWave) {
-                const int lab = llab[j];
-                bool leader = true;
-                for (int q = 0; q < j; ++q) leader &= llab[q] != lab;
-                if (leader) {
-                    double sx = 0.0, sy = 0.0;
-                    int k = 0;
-                    for (int q = j; q < n; ++q)
-                        if (llab[q] == lab) {
-                            sx += lwx[q];
-                            sy += lwy[q];
-                            ++k;
-                        }
-                    const double nn = a.cnt[lab], tot = nn + (double)k;
-                    a.y[lab] = sx / tot + a.y[lab] * nn / tot;
-                    a.y[a.L + lab] = sy / tot + a.y[a.L + lab] * nn / tot;
-                    a.cnt[lab] = tot;
-                }
-            }
-            __threadfence_block();
-            for (int j = lane; j < n; j += kWave) {  // y[:, c] after the update (scripts/ICM_ROS.py:117-118)
-                ltx[j] = a.y[llab[j]];
-                lty[j] = a.y[a.L + llab[j]];
-            }
-            __builtin_amdgcn_wave_barrier();
-            // The one-sided solve (fun_x / minimizar_x, scripts/ICM_ROS.py:254-278) in the moment form the sweeps use (round 4;
-            // the per-beam sum with a wave reduction per evaluation took 52 us per pose): the wave forms the pose's 14 sums
-            // once, about the prediction (the Nelder-Mead's start), one term per beam (an entry of one beam: no scatter
-            // term); then the folded energy, every lane running the same chain on the same numbers.
-            PoseIn in;
-            in.n = n;
-            in.ua0 = v; in.ua1 = w; in.ut0 = in.ut1 = 0.0;
-            load3(a.odo, a.T, t - 1, in.oa);
-            load3(a.odo, a.T, t, in.ot);
-            in.op[0] = in.op[1] = in.op[2] = 0.0;
-            in.coa = cos(in.oa[2]); in.soa = sin(in.oa[2]); in.cot = 1.0; in.sot = 0.0;
-            in.pox = xc0; in.poy = xc1; in.tho = xc2; in.co = cos(xc2); in.so = sin(xc2);
-            {
-                double m[kMomentCount];
-#pragma unroll
-                for (int q = 0; q < kMomentCount; ++q) m[q] = 0.0;
-                for (int j = lane; j < n; j += kWave) {
-                    const double bxx = a.bx[j0 + j], byy = a.by[j0 + j];
-                    const double wx = ct * bxx - st * byy, wy = st * bxx + ct * byy;
-                    const double rx = (xc0 + wx) - ltx[j], ry = (xc1 + wy) - lty[j];
-                    m[0] += 1.0; m[1] += wx; m[2] += wy; m[3] += rx; m[4] += ry;
-                    m[5] += wx * wx; m[6] += wy * wy; m[7] += wx * wy;
-                    m[8] += wx * rx; m[9] += wy * rx; m[10] += wx * ry; m[11] += wy * ry;
-                    m[12] += rx * rx; m[13] += ry * ry;
-                }
-#pragma unroll
-                for (int q = 0; q < kMomentCount; ++q) in.pm[q] = wave_sum(m[q]);
-                in.pm[14] = in.pm[15] = in.pm[16] = 0.0;
-            }
-            SolveArgs sa;
-            sa.x = a.x; sa.x0 = nullptr; sa.odo = a.odo; sa.u = a.u;
-            sa.T = t + 1;   // (one-sided: pose t is the last one there is)
-            sa.t_begin = 0; sa.nloc = a.T;
-            sa.dt = a.dt; sa.R0 = a.R0; sa.R1 = a.R1; sa.R2 = a.R2; sa.Q0 = a.Q0; sa.Q1 = a.Q1; sa.cte = a.cte;
-            sa.diag = nullptr; sa.rot = nullptr; sa.cs = nullptr; sa.odo_cs = nullptr; sa.epoch = 0; sa.xh = nullptr;
-            sa.ghost_n = 0; sa.ghost_m = nullptr;
-            double r0 = 0.0, r1 = 0.0, r2 = 0.0;
-            const bool iso = a.Q0 == a.Q1 && a.R0 == a.R1;
-            bool ok = false;
-            if (iso) ok = solve_pose_in<true>(sa, t, in, xt, false, r0, r1, r2);
-            if (!ok) solve_pose_in<false>(sa, t, in, xt, false, r0, r1, r2);
-            xt[0] = r0; xt[1] = r1; xt[2] = r2;
+    for (int t = 1; t < a.T; ++t)
+        if (!init_step(a, t, xt, lact, s, lane)) {
+            if (lane == 0) a.flags[0] = 1;
+            break;
         }
-        if (lane == 0) {
-            a.x[3 * (size_t)t] = xt[0];
-            a.x[3 * (size_t)t + 1] = xt[1];
-            a.x[3 * (size_t)t + 2] = xt[2];
-        }
-    }
     if (lane == 0) *a.lact = lact;
+}
+
+// The resumable form (icm_online_advance): samples t_first..T-1 of a sequence that is still growing, from the pose
+// x[t_first - 1] and the device-resident map and lact the previous launch left.  odo / u have row stride ld.  LDS is
+// sized by B (maxb = B <= ICM_MAX_BEAMS: <= 53 KB), since the scans still to come are not known yet.
+__global__ __launch_bounds__(kWave) void k_init_advance(InitArgs a) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const InitLds s = init_lds(smem, a.maxb);
+    const int lane = lane_id();
+    int lact = *a.lact;
+    double xt[3] = {a.x[3 * (size_t)(a.t_first - 1)], a.x[3 * (size_t)(a.t_first - 1) + 1], a.x[3 * (size_t)(a.t_first - 1) + 2]};
+    int t = a.t_first;
+    for (; t < a.T; ++t)
+        if (!init_step(a, t, xt, lact, s, lane)) {
+            if (lane == 0) a.flags[0] = 1;
+            break;
+        }
+    if (lane == 0) {
+        *a.lact = lact;
+        a.flags[1] = t;
+    }
+}
+
+// Offsets of a slice of scans pushed behind the kept beams already there: boff[i] += boff[0] for i = 1..n, from the
+// slice's own exclusive scan (scan[0..n]) -- icm_online_push.
+__global__ __launch_bounds__(kBlock) void k_rebase_offsets(const int* __restrict__ scan, int n, int* __restrict__ boff) {
+    const int i = blockIdx.x * kBlock + threadIdx.x + 1;
+    if (i > n) return;
+    boff[i] = boff[0] + scan[i];
 }
 
 // One explicit solve / energy evaluation (parity tests).  io: see icm_solve_one.

@@ -3,7 +3,11 @@
 sequence named by `config.file` is loaded and `inicializar_offline()` runs the same
 initialisation pass on it.
 
-    python example.py [config.yaml] [data.mat|data.npz]
+    python example.py [--online] [config.yaml] [data.mat|data.npz]
+
+--online: the reference's online front door instead (scripts/ICM_ROS.py:57-119): every sample of the data file is
+replayed as a LaserScan / Odometry message pair (matlab2ros.replay) into ICM.lidar / ICM.odom, and online_step()
+advances the initialisation pass as the samples arrive; online_finish() then hands over to the usual sweeps.
 """
 import sys
 from copy import deepcopy as copy
@@ -23,11 +27,31 @@ class My_method(ICM_ROS):
         ICM_ROS.__init__(self, config)
 
 
+def inicializar_por_mensajes(ICM, file=None):
+    """Replay the data file's samples as messages into the subscribers, one online_step per sample."""
+    from matlab2ros.replay import replay
+    z, odo, vel = ICM.read_data_file(file)
+
+    def on_scan(msg):
+        ICM.lidar.callback(msg)
+        ICM.online_step()
+
+    replay(z, odo, vel, on_scan, ICM.odom.callback)
+    ICM.online_step()
+    ICM.online_finish()
+    print('online: %d samples, %d dropped, %d landmarks' % (ICM.positions.shape[1], ICM.dropped_samples, ICM.mapa_viejo.shape[1]))
+
+
 if __name__ == '__main__':
-    config = ConfigICM(sys.argv[1] if len(sys.argv) > 1 else 'config_default.yaml')
+    args = [a for a in sys.argv[1:] if a != '--online']
+    online = len(args) != len(sys.argv) - 1
+    config = ConfigICM(args[0] if args else 'config_default.yaml')
     ICM = ICM_ROS(config)
-    ICM.load_data(sys.argv[2] if len(sys.argv) > 2 else None)
-    ICM.inicializar_offline()
+    if online:
+        inicializar_por_mensajes(ICM, args[1] if len(args) > 1 else None)
+    else:
+        ICM.load_data(args[1] if len(args) > 1 else None)
+        ICM.inicializar_offline()
     if ICM.iterations_flag:
         mapa_viejo = copy(ICM.mapa_viejo)
         x = copy(ICM.positions)

@@ -83,6 +83,12 @@ SIGNATURES = {
     "icm_cluster_first_scan": (C.c_int, [_dp, C.c_int64, C.c_double, _ip]),
     "icm_associate": (C.c_int, [_H, _dp, C.c_int64, _dp, C.c_int64, _dp, _dp, _lp, _lp]),
     "icm_init_pass": (C.c_int, [_H, _dp, _dp, _dp, _lp, _dp]),
+    "icm_online_begin": (C.c_int, [_H, _dp, _dp, C.c_int64, C.c_int64]),
+    "icm_online_push": (C.c_int, [_H, _dp, _dp, _dp, C.c_int64, _lp]),
+    "icm_online_seed": (C.c_int, [_H, _dp, _dp, _dp, C.c_int64]),
+    "icm_online_advance": (C.c_int, [_H, C.c_int64, _dp, _lp]),
+    "icm_online_state": (C.c_int, [_H, _dp, _dp, _dp, _lp, _lp]),
+    "icm_online_finish": (C.c_int, [_H]),
     "icm_filtrar": (C.c_int, [C.POINTER(IcmConfig), _dp, _dp, C.c_int64, _dp, _dp, _lp]),
     "icm_enable_timing": (C.c_int, [_H, C.c_int]),
     "icm_reset_timing": (C.c_int, [_H]),

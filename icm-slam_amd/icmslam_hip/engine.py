@@ -73,6 +73,28 @@ def cluster_first_scan(points, t):
     return lab
 
 
+def seed_first_scan(config, x0, bx, by):
+    """The map the causal pass starts from (`Mapa.actualizar` with no landmark yet, reference
+    scripts/ICM_SLAM_tools.py:160-165): scan 0's kept beams (body points bx, by) projected with x0, clustered, and the
+    clusters' centres and sizes.  Returns (y (2,L), counts (L), landmarks_actuales, labels c).  Shared by the offline
+    pass and the online one, so both start from the same bits."""
+    L = int(config.L)
+    x0 = _f64(np.asarray(x0, dtype=np.float64).reshape(3))
+    bx, by = _f64(bx), _f64(by)
+    if bx.shape[0] == 0:
+        raise ValueError("the first scan has no kept beam: nothing to seed the map with")
+    ct, st = np.cos(x0[2] - np.pi / 2.0), np.sin(x0[2] - np.pi / 2.0)
+    w = np.stack(((bx * ct - by * st) + x0[0], (bx * st + by * ct) + x0[1]), axis=1)
+    c = cluster_first_scan(w, config.dist_thr)
+    y = np.zeros((2, L))
+    cnt = np.zeros(L)
+    lact = int(c.max()) + 1
+    for i in range(lact):          # cluster centres and sizes (scripts/ICM_SLAM_tools.py:163-165)
+        y[:, i] = np.mean(w[c == i, :], axis=0)
+        cnt[i] = np.sum(c == i)
+    return y, cnt, lact, c
+
+
 _PREFILTER_ENGINES = {}
 _SCAN_ENGINES = {}
 
@@ -243,21 +265,93 @@ class SweepEngine:
         x0 = _f64(np.asarray(x0, dtype=np.float64).reshape(3))
         off, bk, d, bx, by = self.kept_beams()
         n0 = int(off[1] - off[0])
-        if n0 == 0:
-            raise ValueError("the first scan has no kept beam: nothing to seed the map with")
-        ct, st = np.cos(x0[2] - np.pi / 2.0), np.sin(x0[2] - np.pi / 2.0)
-        w = np.stack(((bx[:n0] * ct - by[:n0] * st) + x0[0], (bx[:n0] * st + by[:n0] * ct) + x0[1]), axis=1)
-        c = cluster_first_scan(w, self.config.dist_thr)
-        y = np.zeros((2, self.L))
-        cnt = np.zeros(self.L)
-        lact = int(c.max()) + 1
-        for i in range(lact):          # cluster centres and sizes (scripts/ICM_SLAM_tools.py:163-165)
-            y[:, i] = np.mean(w[c == i, :], axis=0)
-            cnt[i] = np.sum(c == i)
+        y, cnt, lact, c = seed_first_scan(self.config, x0, bx[:n0], by[:n0])
         la = C.c_int64(lact)
         x = np.zeros((3, self.T))
         self._chk(self.lib.icm_init_pass(self.h, dptr(x0), dptr(y), dptr(cnt), C.byref(la), dptr(x)))
         return x, y, cnt, int(la.value), c
+
+    # ---- online initialisation ------------------------------------------------------------------
+    # The causal pass on a sequence that grows while it runs (reference inicializar_online, scripts/ICM_ROS.py:57-119):
+    # online_begin, then online_push / online_advance as samples arrive, online_finish before the sweeps.  The sequence,
+    # its kept beams and the running map stay on the GPU; online_finish makes them this engine's sweep sequence.
+    def online_begin(self, B, capacity=1024, x0=None):
+        """Start an online pass with B beams per scan, room for `capacity` samples (the buffers grow as needed).  x0 (3,):
+        pose 0; default the first sample's odometry, as inicializar_offline takes it.  Drops any uploaded sequence."""
+        B = int(B)
+        cosb, sinb, _ = bearing_tables(B, getattr(self.config, "angle_increment", None))
+        self._chk(self.lib.icm_online_begin(self.h, dptr(_f64(cosb)), dptr(_f64(sinb)), B, int(capacity)))
+        self.T, self.B, self.t_begin, self.nloc, self.nnz = 0, B, 0, 0, 0
+        self._online_x0 = None if x0 is None else _f64(np.asarray(x0, dtype=np.float64).reshape(3))
+        self._online_c = None
+        self._online_done = 0
+
+    def online_push(self, scans, odometria, u):
+        """Append n samples: scans (B,n) beam-major like `mediciones`, odometria (3,n), u (2,n).  The scan pre-filter runs
+        on the new scans; the pass does not advance.  The first push seeds the map from scan 0 (ValueError if scan 0 keeps
+        no beam).  Returns the kept beams of everything pushed."""
+        scans = np.asarray(scans, dtype=np.float64)
+        if scans.ndim == 1:
+            scans = scans[:, None]
+        odometria = _f64(np.asarray(odometria, dtype=np.float64).reshape(3, -1))
+        u = _f64(np.asarray(u, dtype=np.float64).reshape(2, -1))
+        n = scans.shape[1]
+        if scans.shape[0] != self.B or odometria.shape[1] != n or u.shape[1] != n:
+            raise ValueError("online_push: scans must be (B,n), odometria (3,n) and u (2,n)")
+        rows = np.ascontiguousarray(scans.T)
+        nnz = C.c_int64(0)
+        self._chk(self.lib.icm_online_push(self.h, dptr(rows), dptr(odometria), dptr(u), n, C.byref(nnz)))
+        first = self.nloc == 0
+        self.nloc += n
+        self.nnz = int(nnz.value)
+        if first and n:
+            if self._online_x0 is None:
+                self._online_x0 = odometria[:, 0].copy()
+            off, bk, d, bx, by = self.kept_beams()
+            n0 = int(off[1] - off[0])
+            y, cnt, lact, c = seed_first_scan(self.config, self._online_x0, bx[:n0], by[:n0])
+            self._chk(self.lib.icm_online_seed(self.h, dptr(self._online_x0), dptr(y), dptr(cnt), lact))
+            self._online_c = c
+            self._online_done = 1
+        return self.nnz
+
+    def online_advance(self, t_end=None):
+        """The causal pass over every pushed sample not yet processed (up to t_end - 1), one launch.  Returns the new
+        poses (3, n).  IndexError if a new landmark does not fit in L (online_state() then holds the samples before it)."""
+        t_end = self.nloc if t_end is None else int(t_end)
+        n = max(t_end - self._online_done, 0)
+        x = np.zeros((3, max(n, 1)))
+        la = C.c_int64(0)
+        rc = self.lib.icm_online_advance(self.h, t_end, dptr(x), C.byref(la))
+        if rc == 0:
+            self._online_done = t_end
+        elif rc == _lib.ICM_ERR_INDEX:   # (the pass stopped at the failing sample)
+            td = C.c_int64(0)
+            self.lib.icm_online_state(self.h, None, None, None, None, C.byref(td))
+            self._online_done = int(td.value)
+        self._chk(rc)
+        return x[:, :n]
+
+    def online_state(self):
+        """Everything processed so far: (x (3,t_done), y_raw (2,L), counts (L), landmarks_actuales, labels of scan 0) --
+        init_pass's tuple, BEFORE Mapa.filtrar."""
+        td = C.c_int64(0)
+        self._chk(self.lib.icm_online_state(self.h, None, None, None, None, C.byref(td)))
+        x = np.zeros((3, int(td.value)))
+        y, cnt = np.zeros((2, self.L)), np.zeros(self.L)
+        la = C.c_int64(0)
+        self._chk(self.lib.icm_online_state(self.h, dptr(x), dptr(y), dptr(cnt), C.byref(la), None))
+        return x, y, cnt, int(la.value), self._online_c
+
+    def samples_processed(self):
+        """Samples through the online pass (pose 0 counts once the map is seeded)."""
+        return self._online_done
+
+    def online_finish(self):
+        """End the online pass: the pushed samples become this engine's sweep sequence (as upload() of the same arrays
+        would leave it, without uploading them again)."""
+        self._chk(self.lib.icm_online_finish(self.h))
+        self.T = self.nloc
 
     # ---- one sweep through host arrays -------------------------------------------------
     def sweep(self, mapa_viejo, x, x0, lact, schedule="sequential"):

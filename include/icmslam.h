@@ -256,6 +256,34 @@ int icm_cluster_first_scan(const double *pts, int64_t n, double t, int32_t *labe
  *   x_out [3*T] the initial poses.  Mapa.filtrar (icm_filtrar) is applied by the caller. */
 int icm_init_pass(icm_handle *h, const double *x0, double *y, double *counts, int64_t *lact, double *x_out);
 
+/* ---- online initialisation (reference inicializar_online / principal_callback, scripts/ICM_ROS.py:57-119) -------- */
+/* The same causal pass as icm_init_pass, on a sequence that grows while it runs; single GPU.  Order:
+ *   icm_online_begin -> icm_online_push (scan 0 at least) -> icm_online_seed -> { icm_online_push | icm_online_advance }*
+ *   -> icm_online_finish -> the sweeps (icm_set_state / icm_sweep_device / icm_sweep ...).
+ * Call-order errors are ICM_ERR_ARG with a message in icm_last_error; the handle stays usable.
+ * One push of the whole sequence and one advance give exactly icm_init_pass's numbers. */
+/* Drops any uploaded sequence and online state (as icm_upload does), fixes B (same limits as icm_upload) and the
+ * bearing tables cosb / sinb [B], reserves room for capacity_hint samples (the buffers grow, doubling, as needed).
+ * ICM_ERR_ARG on a sharded handle. */
+int icm_online_begin(icm_handle *h, const double *cosb, const double *sinb, int64_t B, int64_t capacity_hint);
+/* Appends n samples: ranges [n*B] pose-major, odo (3,n), u (2,n) row-major.  Runs the scan pre-filter on the new scans
+ * only (kept beams bit for bit as icm_prefilter over the whole sequence); does not advance the pass.  One host
+ * synchronisation per call.  *nnz_out (nullable) = kept beams of all samples pushed. */
+int icm_online_push(icm_handle *h, const double *ranges, const double *odo, const double *u, int64_t n, int64_t *nnz_out);
+/* Pose 0 (x0 [3]) and the map seeded from scan 0's clusters (y (2,L), counts (L), lact) become the device-resident
+ * running state; samples processed := 1.  Needs scan 0 pushed. */
+int icm_online_seed(icm_handle *h, const double *x0, const double *y, const double *counts, int64_t lact);
+/* The causal pass over samples t_done..t_end-1 in one launch (k_init_advance); t_end <= samples pushed.  x_new
+ * (3, t_end - t_done) receives the new poses, *lact_out (nullable) landmarks in use.  ICM_ERR_INDEX if a new landmark
+ * does not fit in L at sample t: samples processed := t, the state up to there stays readable (icm_online_state). */
+int icm_online_advance(icm_handle *h, int64_t t_end, double *x_new, int64_t *lact_out);
+/* Everything processed so far (nullable outputs): x (3, t_done) poses, y (2,L) / counts (L) / lact the raw map before
+ * Mapa.filtrar, *t_done samples processed. */
+int icm_online_state(icm_handle *h, double *x, double *y, double *counts, int64_t *lact, int64_t *t_done);
+/* Ends the online mode: the pushed samples (>= 2) become the handle's sweep sequence, as icm_upload of all of them +
+ * icm_prefilter would leave it, without a second upload. */
+int icm_online_finish(icm_handle *h);
+
 /* ---- host-side map prune/merge (no GPU needed) ----------------------------------------- */
 /* Mapa.filtrar (reference scripts/ICM_SLAM_tools.py:204-265): y (2,L) row-major, counts (L),
  * lact in/out.  y_out (2,L) zero padded, counts_out (L). */
