@@ -260,6 +260,8 @@ struct icm_handle {
     bool opt_req = false;      // asked for: by icm_sweep_classic for its first attempt, by icm_set_optimistic for the phase calls
     DevBuf<double> rot;   // (cos, sin)(theta - pi/2) per pose of the shard, refreshed at the start of every sweep (k_pose_rot)
     hipEvent_t ev_map = nullptr, ev_copied = nullptr;
+    hipEvent_t ev_batch = nullptr;   // icm_sweep_batch: this member's phases are queued / the batch's chain launch is
+    DevBuf<SolveArgs> batch_desc;    // icm_sweep_batch: the descriptors of a batch whose chains run on this handle's stream
     // online initialisation (icm_online_*): a sequence that grows in place and the causal pass over it.  While it runs,
     // odo / u are (3,on_cap) / (2,on_cap) (row stride = capacity), the per-scan buffers hold on_n scans and nloc = on_n.
     bool online = false, on_finished = false, on_seeded = false;
@@ -414,6 +416,7 @@ int icm_create(const icm_config* cfg, int device, icm_handle** out) {
         (e = create_solve_stream(&h->solve_stream)) != hipSuccess ||
         (e = hipEventCreateWithFlags(&h->ev_map, hipEventDisableTiming)) != hipSuccess ||
         (e = hipEventCreateWithFlags(&h->ev_copied, hipEventDisableTiming)) != hipSuccess ||
+        (e = hipEventCreateWithFlags(&h->ev_batch, hipEventDisableTiming)) != hipSuccess ||
         (e = hipEventCreateWithFlags(&h->ev_cmp, hipEventDisableTiming)) != hipSuccess ||
         (e = hipEventCreateWithFlags(&h->ev_gh0, hipEventDisableTiming)) != hipSuccess || (e = hipEventCreateWithFlags(&h->ev_gh1, hipEventDisableTiming)) != hipSuccess ||
         (e = hipHostMalloc(reinterpret_cast<void**>(&h->pin_i), 64 * sizeof(int), hipHostMallocMapped)) != hipSuccess ||
@@ -494,6 +497,8 @@ int icm_destroy(icm_handle* h) {
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->ev_map) (void)hipEventDestroy(h->ev_map);
     if (h->ev_copied) (void)hipEventDestroy(h->ev_copied);
+    if (h->ev_batch) (void)hipEventDestroy(h->ev_batch);
+    h->batch_desc.release();
     if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
     if (h->solve_stream) { (void)hipStreamSynchronize(h->solve_stream); (void)hipStreamDestroy(h->solve_stream); }
     h->pre_x.release(); h->pre_y.release(); h->pre_n.release();
@@ -1574,11 +1579,9 @@ static int launch_fused_solve(icm_handle* h, SolveArgs a, SolveSeg g, hipStream_
     return ICM_OK;
 }
 
-int icm_sweep_solve(icm_handle* h, int schedule, int colour) {
-    if (!h) return ICM_ERR_ARG;
-    if (!h->have_state) FAIL(h, ICM_ERR_ARG, "icm_sweep_solve: no state");
-    if (h->scan0_empty) return ICM_OK;
-    HIPCHK(h, hipSetDevice(h->device));
+// Bookkeeping in front of a solve launch, on h->stream (icm_sweep_solve; icm_sweep_batch in front of the member's event,
+// which its batch's chain launch waits for).
+static int solve_prologue(icm_handle* h) {
     if (h->x_check_wait) {    // the check of the caller's poses against the device's (k_x_compare, side stream): done long ago
         HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_cmp, 0));
         h->x_check_wait = false;
@@ -1589,6 +1592,35 @@ int icm_sweep_solve(icm_handle* h, int schedule, int colour) {
     }
     h->mirror_host = nullptr;   // (poses about to change on the device; icm_sweep says when the caller's array has them too)
     h->x_mirrored = false;
+    return ICM_OK;
+}
+
+// The reference-order chain in moment form folds the energy (FOLD) with isotropic weights, unless icm_set_fold_mode says.
+static bool seq_chain_fold(const icm_handle* h) {
+    const bool iso = h->cfg.Q[0] == h->cfg.Q[1] && h->cfg.R[0] == h->cfg.R[1];
+    return h->fold_mode < 0 ? iso : h->fold_mode == 1;
+}
+
+// ... and behind a reference-order chain in moment form (k_solve_m_sequential, k_solve_m_sequential_batch)
+static void seq_chain_epilogue(icm_handle* h) {
+    h->rot_valid = false;   // (the chain does not keep the rotation pairs: k_pose_rot at the head of the next sweep)
+}
+
+// A chain launch timed by the caller's events (icm_sweep_batch), booked like TIMED books the single launch.
+static void add_solve_time(icm_handle* h, float ms) {
+    h->k_ms[KID_SOLVE] += ms;
+    h->k_n[KID_SOLVE] += 1;
+}
+
+int icm_sweep_solve(icm_handle* h, int schedule, int colour) {
+    if (!h) return ICM_ERR_ARG;
+    if (!h->have_state) FAIL(h, ICM_ERR_ARG, "icm_sweep_solve: no state");
+    if (h->scan0_empty) return ICM_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    {
+        int rcp = solve_prologue(h);
+        if (rcp) return rcp;
+    }
     const bool ph = h->phase_timing && h->optimistic;
     if (ph) (void)hipEventRecord(h->ev_ph[3], h->stream);
     SolveArgs a = solve_args(h);
@@ -1614,11 +1646,10 @@ int icm_sweep_solve(icm_handle* h, int schedule, int colour) {
         if (h->form == 1) TIMED(h, KID_SOLVE, (k_solve_sequential<true><<<1, kWave, 0, h->stream>>>(a)));
         else if (h->form == 2) TIMED(h, KID_SOLVE, (k_solve_sequential<false><<<1, kWave, 0, h->stream>>>(a)));
         else {
-            const bool iso = h->cfg.Q[0] == h->cfg.Q[1] && h->cfg.R[0] == h->cfg.R[1];
-            const bool fold = h->fold_mode < 0 ? iso : h->fold_mode == 1;
+            const bool fold = seq_chain_fold(h);
             if (fold) TIMED(h, KID_SOLVE, (k_solve_m_sequential<true><<<1, kWave, 0, h->stream>>>(a)));
             else TIMED(h, KID_SOLVE, (k_solve_m_sequential<false><<<1, kWave, 0, h->stream>>>(a)));
-            h->rot_valid = false;   // (the chain does not keep the rotation pairs: k_pose_rot at the head of the next sweep)
+            seq_chain_epilogue(h);
         }
     } else if (schedule == ICM_SCHEDULE_REDBLACK && colour < 0 && h->form == 0 && h->fuse_colours) {
         // both colours in one launch, even waves chase the odd ones (a shard: its ghost pose is the first odd pose)
@@ -2517,6 +2548,276 @@ int icm_init_pass(icm_handle* h, const double* x0, double* y, double* counts, in
         x_out[T + t] = xt[3 * t + 1];
         x_out[2 * T + t] = xt[3 * t + 2];
     }
+    return ICM_OK;
+}
+
+// ---- many independent sequences, one launch per chain form ----------------------------------------------------------
+// icm_init_pass_batch / icm_sweep_batch: every member is a handle of its own (its sequence, config, map and stream); the
+// chains of all members go into one launch (two for a sweep batch that mixes the folded and the complete energy), one
+// wave per member.  Descriptors are built for every call (a member's buffers move with icm_set_state or an upload) and
+// sorted by descending T, so that the longest chains start first when the batch outgrows the resident waves.
+
+// A malformed batch: the message goes to every member, nothing is queued and rc_out is not written.
+static int batch_refuse(icm_handle* const* hs, int M, int code, const std::string& msg) {
+    for (int i = 0; i < M; ++i)
+        if (hs[i]) hs[i]->err = msg;
+    return code;
+}
+
+static int batch_check(icm_handle* const* hs, int M, bool need_state, const char* fn) {
+    const std::string f(fn);
+    if (!hs || M < 1) {
+        g_create_err = f + ": needs M >= 1 handles";
+        return ICM_ERR_ARG;
+    }
+    for (int i = 0; i < M; ++i)
+        if (!hs[i]) return batch_refuse(hs, M, ICM_ERR_ARG, f + ": null handle in the batch");
+    std::vector<icm_handle*> sorted(hs, hs + M);
+    std::sort(sorted.begin(), sorted.end());
+    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
+        return batch_refuse(hs, M, ICM_ERR_ARG, f + ": the same handle twice in one batch");
+    for (int i = 0; i < M; ++i) {
+        const icm_handle* h = hs[i];
+        const std::string who = f + ": member " + std::to_string(i);
+        if (h->device != hs[0]->device) return batch_refuse(hs, M, ICM_ERR_ARG, who + " is on another device than member 0");
+        if (!h->prefiltered) return batch_refuse(hs, M, ICM_ERR_ARG, who + " has no prefiltered sequence (icm_upload + icm_prefilter)");
+        if (need_state && !h->have_state) return batch_refuse(hs, M, ICM_ERR_ARG, who + " has no state (icm_set_state)");
+    }
+    for (int i = 0; i < M; ++i) {
+        const icm_handle* h = hs[i];
+        const std::string who = f + ": member " + std::to_string(i);
+        if (h->world > 1) return batch_refuse(hs, M, ICM_ERR_UNSUPPORTED, who + " is a shard of a multi-rank job; a batch is single-rank");
+        if (h->form != 0 || h->debug)
+            return batch_refuse(hs, M, ICM_ERR_UNSUPPORTED, who + " uses a cross-check energy form or debug mode; a batch runs the moment form only");
+        if (h->opt_req) return batch_refuse(hs, M, ICM_ERR_UNSUPPORTED, who + " is in optimistic mode (icm_set_optimistic); a batch sweep is careful");
+    }
+    return ICM_OK;
+}
+
+int icm_init_pass_batch(icm_handle* const* hs, int M, const double* const* x0, double* const* y, double* const* counts,
+                        int64_t* lact, double* const* x_out, int* rc_out) {
+    int rc = batch_check(hs, M, false, "icm_init_pass_batch");
+    if (rc) return rc;
+    if (!x0 || !y || !counts || !lact || !x_out || !rc_out)
+        return batch_refuse(hs, M, ICM_ERR_ARG, "icm_init_pass_batch: null pointer");
+    for (int i = 0; i < M; ++i)
+        if (!x0[i] || !y[i] || !counts[i] || !x_out[i]) return batch_refuse(hs, M, ICM_ERR_ARG, "icm_init_pass_batch: null pointer");
+    // what icm_init_pass checks of one member fails that member only
+    std::vector<int> maxb(M, 1), go;
+    for (int i = 0; i < M; ++i) {
+        icm_handle* h = hs[i];
+        rc_out[i] = ICM_OK;
+        if (h->t_begin != 0 || h->nloc != h->T) {
+            h->err = "icm_init_pass: the causal pass is one chain; it needs the whole sequence on one GPU";
+            rc_out[i] = ICM_ERR_UNSUPPORTED;
+            continue;
+        }
+        if (lact[i] <= 0 || lact[i] > h->cfg.L) {
+            h->err = "icm_init_pass: seed the map with the first scan's clusters (icm_cluster_first_scan)";
+            rc_out[i] = ICM_ERR_ARG;
+            continue;
+        }
+        for (int64_t t = 0; t < h->T; ++t) maxb[i] = std::max(maxb[i], h->h_boff[(size_t)t + 1] - h->h_boff[(size_t)t]);
+        if ((size_t)maxb[i] * (4 * sizeof(double) + sizeof(int)) > 160 * 1024) {
+            h->err = "icm_init_pass: too many kept beams per scan for the LDS staging";
+            rc_out[i] = ICM_ERR_UNSUPPORTED;
+            continue;
+        }
+        go.push_back(i);
+    }
+    if (!go.empty()) {
+        std::stable_sort(go.begin(), go.end(), [&](int p, int q) { return hs[p]->T > hs[q]->T; });
+        icm_handle* h0 = hs[go[0]];
+        const hipStream_t st = h0->stream;
+        const size_t n = go.size();
+        // one arena: descriptors | per member x (T,3), y (2,L), counts (L) | per member [lact, overflow]
+        const size_t desc_bytes = (n * sizeof(InitArgs) + 255) / 256 * 256;
+        std::vector<size_t> doff(n);
+        size_t nd = 0;
+        int lds_max = 1;
+        for (size_t k = 0; k < n; ++k) {
+            const icm_handle* h = hs[go[k]];
+            doff[k] = nd;
+            nd += 3 * (size_t)h->T + 3 * (size_t)h->cfg.L;
+            lds_max = std::max(lds_max, maxb[go[k]]);
+        }
+        const size_t lds = (size_t)lds_max * (4 * sizeof(double) + sizeof(int));
+        const size_t words_off = desc_bytes + nd * sizeof(double);
+        const size_t total = words_off + 2 * n * sizeof(int);
+        std::vector<unsigned char> stage(total, 0);
+        unsigned char* base = nullptr;
+        hipError_t e = hipSetDevice(h0->device);
+        for (size_t k = 0; k + 1 < n && e == hipSuccess; ++k) {   // (whatever the other members' streams still hold)
+            icm_handle* h = hs[go[k + 1]];
+            if (h->stream == st) continue;
+            e = hipEventRecord(h->ev_batch, h->stream);
+            if (e == hipSuccess) e = hipStreamWaitEvent(st, h->ev_batch, 0);
+        }
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&base), total);
+        if (e == hipSuccess) {
+            InitArgs* desc = reinterpret_cast<InitArgs*>(stage.data());
+            double* hd = reinterpret_cast<double*>(stage.data() + desc_bytes);
+            int* hw = reinterpret_cast<int*>(stage.data() + words_off);
+            double* dd = reinterpret_cast<double*>(base + desc_bytes);
+            int* dw = reinterpret_cast<int*>(base + words_off);
+            for (size_t k = 0; k < n; ++k) {
+                const int i = go[k];
+                const icm_handle* h = hs[i];
+                const size_t T = (size_t)h->T, L = (size_t)h->cfg.L;
+                double* hx = hd + doff[k];
+                hx[0] = x0[i][0]; hx[1] = x0[i][1]; hx[2] = x0[i][2];
+                std::copy(y[i], y[i] + 2 * L, hx + 3 * T);
+                std::copy(counts[i], counts[i] + L, hx + 3 * T + 2 * L);
+                hw[2 * k] = (int)lact[i];
+                InitArgs& a = desc[k];
+                a.x = dd + doff[k]; a.odo = h->odo.p; a.u = h->u.p; a.T = (int)T; a.ld = (int)T; a.t_first = 1;
+                a.boff = h->boff.p; a.bx = h->bx.p; a.by = h->by.p;
+                a.y = a.x + 3 * T; a.cnt = a.y + 2 * L; a.lact = dw + 2 * k; a.L = (int)L; a.maxb = maxb[i]; a.thr = h->cfg.dist_thr;
+                a.dt = h->cfg.deltat; a.R0 = h->cfg.R[0]; a.R1 = h->cfg.R[1]; a.R2 = h->cfg.R[2];
+                a.Q0 = h->cfg.Q[0]; a.Q1 = h->cfg.Q[1]; a.cte = h->cfg.cte_odom; a.flags = dw + 2 * k + 1;
+            }
+            e = hipMemcpyAsync(base, stage.data(), total, hipMemcpyHostToDevice, st);
+            if (e == hipSuccess)
+                e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_init_pass_batch), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (e == hipSuccess) {
+                k_init_pass_batch<<<(unsigned)n, kWave, lds, st>>>(reinterpret_cast<const InitArgs*>(base));
+                e = hipGetLastError();
+            }
+            if (e == hipSuccess)
+                e = hipMemcpyAsync(stage.data() + desc_bytes, base + desc_bytes, total - desc_bytes, hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess) e = hipStreamSynchronize(st);
+            const hipError_t ef = hipFree(base);
+            if (e == hipSuccess) e = ef;
+            if (e == hipSuccess)
+                for (size_t k = 0; k < n; ++k) {
+                    const int i = go[k];
+                    icm_handle* h = hs[i];
+                    const size_t T = (size_t)h->T, L = (size_t)h->cfg.L;
+                    const double* hx = hd + doff[k];
+                    std::copy(hx + 3 * T, hx + 3 * T + 2 * L, y[i]);   // (the map as the pass left it, also when it failed: as icm_init_pass)
+                    std::copy(hx + 3 * T + 2 * L, hx + 3 * T + 3 * L, counts[i]);
+                    if (hw[2 * k + 1]) {
+                        h->err = "init pass: new landmarks exceed the map capacity L (the reference raises IndexError, scripts/ICM_SLAM_tools.py:191)";
+                        rc_out[i] = ICM_ERR_INDEX;
+                        continue;
+                    }
+                    lact[i] = hw[2 * k];
+                    for (size_t t = 0; t < T; ++t) {
+                        x_out[i][t] = hx[3 * t];
+                        x_out[i][T + t] = hx[3 * t + 1];
+                        x_out[i][2 * T + t] = hx[3 * t + 2];
+                    }
+                }
+        }
+        if (e != hipSuccess)
+            for (int i : go) {
+                hs[i]->err = std::string("icm_init_pass_batch: ") + hipGetErrorString(e);
+                rc_out[i] = ICM_ERR_HIP;
+            }
+    }
+    for (int i = 0; i < M; ++i)
+        if (rc_out[i]) return rc_out[i];
+    return ICM_OK;
+}
+
+int icm_sweep_batch(icm_handle* const* hs, int M, int schedule, int* rc_out) {
+    int rc = batch_check(hs, M, true, "icm_sweep_batch");
+    if (rc) return rc;
+    if (!rc_out) return batch_refuse(hs, M, ICM_ERR_ARG, "icm_sweep_batch: null pointer");
+    if (schedule == ICM_SCHEDULE_REDBLACK)
+        return batch_refuse(hs, M, ICM_ERR_UNSUPPORTED, "icm_sweep_batch: a red-black sweep is parallel already; a batch runs the sequential schedule");
+    if (schedule != ICM_SCHEDULE_SEQUENTIAL) return batch_refuse(hs, M, ICM_ERR_ARG, "icm_sweep_batch: unknown schedule");
+    // 1. every member's own phases on its own stream, Mapa.filtrar deferred as icm_sweep_classic defers it
+    std::vector<int> fold_m, full_m;
+    for (int i = 0; i < M; ++i) {
+        icm_handle* h = hs[i];
+        int r = icm_sweep_local(h);
+        h->defer_filtrar = true;
+        if (!r) r = icm_sweep_targets(h);
+        h->defer_filtrar = false;
+        if (!r && !h->scan0_empty) {
+            r = solve_prologue(h);
+            if (!r) (seq_chain_fold(h) ? fold_m : full_m).push_back(i);
+        }
+        rc_out[i] = r;
+    }
+    // 2. one event per member, the chain launches behind all of them on the stream of the first member in the launch
+    const size_t nf = fold_m.size(), n = nf + full_m.size();
+    if (n) {
+        const auto longer = [&](int p, int q) { return hs[p]->T > hs[q]->T; };
+        std::stable_sort(fold_m.begin(), fold_m.end(), longer);
+        std::stable_sort(full_m.begin(), full_m.end(), longer);
+        std::vector<int> chain(fold_m);
+        chain.insert(chain.end(), full_m.begin(), full_m.end());
+        std::vector<SolveArgs> desc(n);
+        bool timed = false;
+        for (size_t k = 0; k < n; ++k) {
+            icm_handle* h = hs[chain[k]];
+            SolveArgs a = solve_args(h);   // (as icm_sweep_solve: no diagnostics, moment form keeps its rotation table pointer)
+            a.diag = nullptr;
+            a.rot = h->rot.p;
+            desc[k] = a;
+            timed |= h->timing;
+        }
+        icm_handle* h0 = hs[chain[0]];
+        const hipStream_t st = h0->stream;
+        hipError_t e = hipSetDevice(h0->device);
+        // the descriptors first, into the launch member's buffer (stream-ordered behind any earlier batch that used it):
+        // their host copy must be consumed before this call returns, and the stream holds only h0's own phases here
+        if (e == hipSuccess) e = h0->batch_desc.reserve(n);
+        SolveArgs* const d = h0->batch_desc.p;
+        if (e == hipSuccess) e = hipMemcpyAsync(d, desc.data(), n * sizeof(SolveArgs), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        for (size_t k = 1; k < n && e == hipSuccess; ++k) {
+            icm_handle* h = hs[chain[k]];
+            if (h->stream == st) continue;
+            e = hipEventRecord(h->ev_batch, h->stream);
+            if (e == hipSuccess) e = hipStreamWaitEvent(st, h->ev_batch, 0);
+        }
+        if (e == hipSuccess && timed) e = hipEventRecord(h0->ev0, st);
+        if (e == hipSuccess && nf) {
+            k_solve_m_sequential_batch<true><<<(unsigned)nf, kWave, 0, st>>>(d);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess && n > nf) {
+            k_solve_m_sequential_batch<false><<<(unsigned)(n - nf), kWave, 0, st>>>(d + nf);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess && timed) e = hipEventRecord(h0->ev1, st);
+        if (e == hipSuccess) e = hipEventRecord(h0->ev_batch, st);
+        // 3. every member's stream waits for the launch
+        for (size_t k = 1; k < n && e == hipSuccess; ++k) {
+            icm_handle* h = hs[chain[k]];
+            if (h->stream != st) e = hipStreamWaitEvent(h->stream, h0->ev_batch, 0);
+        }
+        if (e == hipSuccess && timed) {
+            float ms = 0.f;
+            e = hipEventSynchronize(h0->ev1);
+            if (e == hipSuccess) e = hipEventElapsedTime(&ms, h0->ev0, h0->ev1);
+            if (e == hipSuccess)
+                for (int i : chain)
+                    if (hs[i]->timing) add_solve_time(hs[i], ms);
+        }
+        for (int i : chain) {
+            if (e != hipSuccess) {
+                hs[i]->err = std::string("icm_sweep_batch: chain launch: ") + hipGetErrorString(e);
+                rc_out[i] = ICM_ERR_HIP;
+            } else {
+                seq_chain_epilogue(hs[i]);
+            }
+        }
+    }
+    // ... and then icm_sweep_finish for each member, as icm_sweep_classic ends a sweep
+    for (int i = 0; i < M; ++i) {
+        if (rc_out[i]) continue;
+        icm_handle* h = hs[i];
+        int r = ICM_OK;
+        if (h->filtrar_deferred) r = queue_filtrar(h, true);
+        if (!r) r = icm_sweep_finish(h);
+        rc_out[i] = r;
+    }
+    for (int i = 0; i < M; ++i)
+        if (rc_out[i]) return rc_out[i];
     return ICM_OK;
 }
 

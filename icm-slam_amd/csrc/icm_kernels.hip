@@ -26,8 +26,10 @@
 //   phase C   k_pose_moments[_h]  14 moment sums of the pose's observation energy
 //             k_solve_m_*      Nelder-Mead on the conditional energy in moment form:
 //                              ONE LANE per pose, everything in registers
+//             k_solve_m_sequential[_batch]  the reference-order chain, one lane; _batch: one wave per sequence
 //             k_solve_* (wave per pose, per-beam / per-entry energy): cross-checks
 //   init      k_init_pass      the causal initialisation pass (one wave walks the sequence)
+//             k_init_pass_batch  the same pass over many independent sequences, one wave each (icm_init_pass_batch)
 //             k_init_advance   its resumable form: the samples pushed since the last launch (online initialisation)
 //
 // Mapping: phase A one wavefront per pose (lanes over its runs / its kept beams), entry kernels one DPP
@@ -3252,9 +3254,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(2))) voi
 // solves -- but by k_pose_rot at the head of the next sweep, in parallel (the host clears rot_valid).  data_IJAC2018:
 // 53 -> ?? ms per sweep; the same arithmetic per pose as every other solve form (bit-identical).  (One DPP quad per
 // pose, the four candidate points of an iteration at once, measured slower and was removed: DESIGN.md §5.)
+// This is the chain itself, lane 0 only: k_solve_m_sequential (one sequence, its SolveArgs in the kernel arguments) and
+// k_solve_m_sequential_batch (one wave per sequence of a batch, icm_sweep_batch) both run exactly this.
 template <bool FOLD>
-__global__ __launch_bounds__(kWave) void k_solve_m_sequential(SolveArgs a) {
-    if (threadIdx.x >= 1) return;
+__device__ __forceinline__ void solve_m_sequential_chain(const SolveArgs& a) {
     double prev[3] = {a.x[0], a.x[1], a.x[2]};
     if constexpr (!FOLD) {
         // the complete energy in the loop (anisotropic weights; a cross-check otherwise): load and solve, no prefetch -- with
@@ -3289,6 +3292,21 @@ __global__ __launch_bounds__(kWave) void k_solve_m_sequential(SolveArgs a) {
         prev[0] = r0; prev[1] = r1; prev[2] = r2;
         cur = nxt;
     }
+}
+
+template <bool FOLD>
+__global__ __launch_bounds__(kWave) void k_solve_m_sequential(SolveArgs a) {
+    if (threadIdx.x >= 1) return;
+    solve_m_sequential_chain<FOLD>(a);
+}
+
+// Many independent sequences (icm_sweep_batch): workgroup b walks the chain of descs[b].  The members share nothing --
+// no flags, no spin, no atomics: a workgroup that is not resident yet simply starts when a SIMD frees up.
+template <bool FOLD>
+__global__ __launch_bounds__(kWave) void k_solve_m_sequential_batch(const SolveArgs* __restrict__ descs) {
+    if (threadIdx.x >= 1) return;
+    const SolveArgs a = descs[blockIdx.x];
+    solve_m_sequential_chain<FOLD>(a);
 }
 
 // Red-black half sweep: all poses of one parity (colour = tg & 1) of this shard, one wave
@@ -3514,11 +3532,8 @@ __device__ __forceinline__ bool init_step(const InitArgs& a, int t, double xt[3]
     return true;
 }
 
-// The whole uploaded sequence, t = 1..T-1 (icm_init_pass).  LDS: the sequence's largest kept-beam count.
-__global__ __launch_bounds__(kWave) void k_init_pass(InitArgs a) {
-    extern __shared__ __align__(16) unsigned char smem[];
-    const InitLds s = init_lds(smem, a.maxb);
-    const int lane = lane_id();
+// The whole pass over one sequence, t = 1..T-1 from x[0]: k_init_pass and k_init_pass_batch run exactly this.
+__device__ __forceinline__ void init_pass_chain(const InitArgs& a, const InitLds& s, int lane) {
     int lact = *a.lact;
     double xt[3] = {a.x[0], a.x[1], a.x[2]};
     for (int t = 1; t < a.T; ++t)
@@ -3527,6 +3542,22 @@ __global__ __launch_bounds__(kWave) void k_init_pass(InitArgs a) {
             break;
         }
     if (lane == 0) *a.lact = lact;
+}
+
+// The whole uploaded sequence (icm_init_pass).  LDS: the sequence's largest kept-beam count.
+__global__ __launch_bounds__(kWave) void k_init_pass(InitArgs a) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const InitLds s = init_lds(smem, a.maxb);
+    init_pass_chain(a, s, lane_id());
+}
+
+// Many independent sequences (icm_init_pass_batch): workgroup b runs the pass of descs[b] with its own map, lact and
+// flags.  LDS is sized by the batch's largest maxb; each member lays out its scan by its own.  No member waits on another.
+__global__ __launch_bounds__(kWave) void k_init_pass_batch(const InitArgs* __restrict__ descs) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const InitArgs a = descs[blockIdx.x];
+    const InitLds s = init_lds(smem, a.maxb);
+    init_pass_chain(a, s, lane_id());
 }
 
 // The resumable form (icm_online_advance): samples t_first..T-1 of a sequence that is still growing, from the pose

@@ -83,6 +83,9 @@ SIGNATURES = {
     "icm_cluster_first_scan": (C.c_int, [_dp, C.c_int64, C.c_double, _ip]),
     "icm_associate": (C.c_int, [_H, _dp, C.c_int64, _dp, C.c_int64, _dp, _dp, _lp, _lp]),
     "icm_init_pass": (C.c_int, [_H, _dp, _dp, _dp, _lp, _dp]),
+    "icm_init_pass_batch": (C.c_int, [C.POINTER(_H), C.c_int, C.POINTER(_dp), C.POINTER(_dp), C.POINTER(_dp), _lp,
+                                       C.POINTER(_dp), _ip]),
+    "icm_sweep_batch": (C.c_int, [C.POINTER(_H), C.c_int, C.c_int, _ip]),
     "icm_online_begin": (C.c_int, [_H, _dp, _dp, C.c_int64, C.c_int64]),
     "icm_online_push": (C.c_int, [_H, _dp, _dp, _dp, C.c_int64, _lp]),
     "icm_online_seed": (C.c_int, [_H, _dp, _dp, _dp, C.c_int64]),

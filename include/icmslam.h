@@ -256,6 +256,26 @@ int icm_cluster_first_scan(const double *pts, int64_t n, double t, int32_t *labe
  *   x_out [3*T] the initial poses.  Mapa.filtrar (icm_filtrar) is applied by the caller. */
 int icm_init_pass(icm_handle *h, const double *x0, double *y, double *counts, int64_t *lact, double *x_out);
 
+/* ---- many independent sequences, one launch per chain form ------------------------------------------------------ */
+/* Many independent sequences, one launch per chain form.  hs: M >= 1 DISTINCT handles on one device, single rank,
+ * moment-form energy.  Every member gets exactly what the single call would give it; rc_out[M] receives each member's
+ * own code (its message in that member's icm_last_error).  Returns ICM_OK if every member succeeded, else the code of
+ * the lowest-index failing member.
+ * A malformed batch -- M < 1, a null pointer, the same handle twice, members on different devices, a member without a
+ * prefiltered sequence (icm_sweep_batch: or without state) [ICM_ERR_ARG]; a sharded member, a cross-check energy form
+ * (icm_set_energy_form), debug or optimistic mode [ICM_ERR_UNSUPPORTED] -- is refused before anything is queued: the
+ * message goes to every member, rc_out is not written and no member's state changes.  A data error (a new landmark that
+ * does not fit in L, a label >= L) fails its member only; the others go on.
+ * icm_init_pass_batch: icm_init_pass of every member (x0[i] [3], y[i] (2,L), counts[i] (L), lact[i], x_out[i] (3,T)),
+ * in one launch of one wave per member, through one device arena with one copy each way. */
+int icm_init_pass_batch(icm_handle *const *hs, int M, const double *const *x0, double *const *y,
+                        double *const *counts, int64_t *lact, double *const *x_out, int *rc_out);
+/* One sweep of every member from its resident state (icm_set_state), as icm_sweep_device(h, schedule) would do it.
+ * schedule: ICM_SCHEDULE_SEQUENTIAL only (a red-black sweep is already parallel: ICM_ERR_UNSUPPORTED).
+ * Each member's phase A and targets run on its own stream; the chains of all members follow in one launch per energy
+ * form (folded for isotropic weights, complete otherwise), behind all of them; every member's stream then waits for it. */
+int icm_sweep_batch(icm_handle *const *hs, int M, int schedule, int *rc_out);
+
 /* ---- online initialisation (reference inicializar_online / principal_callback, scripts/ICM_ROS.py:57-119) -------- */
 /* The same causal pass as icm_init_pass, on a sequence that grows while it runs; single GPU.  Order:
  *   icm_online_begin -> icm_online_push (scan 0 at least) -> icm_online_seed -> { icm_online_push | icm_online_advance }*
